@@ -24,8 +24,12 @@ in-place reduction y += x of the same payload and the reported value is
 2*S/t (bytes of the two operands over time); this N=1 semantics is
 recorded in config.n1_semantics.
 
-Also reports submit->launch p50 latency (ms) through the local executor
-(single process task path), mirroring BASELINE.md's second metric.
+A plain run sets up, warms up, times the K steps and prints the result
+line.  `--full` additionally reports submit->launch p50 latency (ms)
+through the local executor (single process task path), mirroring
+BASELINE.md's second metric.  `--dump-outputs DIR` writes what the last
+timed step left in the reduced buffer to DIR/<name>.npy (float32); the
+inputs are seeded, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -55,6 +59,34 @@ def measure_submit_launch_p50(samples: int = 10):
         return None
 
 
+SEED = 20240611
+DUMP_MAX_ELEMS = 4 << 20  # 16 MiB of float32 per dumped array
+
+
+def dump_outputs(dirname: str, arrays: dict) -> None:
+    """Write each 1-D tensor as DIR/<name>.npy in float32.  An array
+    longer than DUMP_MAX_ELEMS is reduced to a fixed, seeded sample of
+    its elements (sorted indices, so the sample keeps buffer order).
+
+    The step accumulates in place, so the dump is the buffer after all
+    (warmup + steps) * ops_per_step operations.  At N=1 a bf16
+    accumulator stops changing once x falls below half an ulp of y
+    (a few hundred adds); runs with few steps and --reps-per-step 1
+    give the most sensitive comparison."""
+    import numpy as np
+    import torch
+
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        n = t.numel()
+        if n > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(SEED).integers(
+                0, n, size=DUMP_MAX_ELEMS))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(dirname, name + ".npy"),
+                t.to(torch.float32).cpu().numpy())
+
+
 def main() -> int:
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
@@ -67,6 +99,12 @@ def main() -> int:
                         "sized so a step is ~tens of ms and the smi "
                         "sampler can observe the timed region)")
     p.add_argument("--latency-samples", type=int, default=10)
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline figure does not "
+                        "need (submit->launch p50 through the executor)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the buffer the last "
+                        "step produced to DIR/<name>.npy (float32)")
     args = p.parse_args()
 
     import torch
@@ -90,6 +128,8 @@ def main() -> int:
     numel = payload_mb * (1 << 20) // 2  # bf16 = 2 bytes
     payload_bytes = numel * 2
 
+    # seeded inputs (per rank): identical from run to run
+    torch.manual_seed(SEED + comm.rank)
     x = torch.randn(numel, dtype=torch.float32, device=dev).to(torch.bfloat16)
     y = None
     if world == 1:
@@ -108,6 +148,14 @@ def main() -> int:
         # ~2 ms already, so 16 reps suffice.
         reps = (128 if world == 1 else 16) if on_gpu else 1
 
+    # a GPU run is only meaningful on a built tree: like smoke(), fail
+    # loudly when the HIP ops library is missing instead of timing a
+    # half-built checkout
+    if on_gpu:
+        from shipyard_amd import ops
+
+        ops.require_native()
+
     def step() -> None:
         if world > 1:
             for _ in range(reps):
@@ -116,9 +164,9 @@ def main() -> int:
             for _ in range(reps):
                 y.add_(x)
 
-    # submit->launch p50 (rank 0 only, before the timed region)
+    # submit->launch p50 (--full, rank 0 only, before the timed region)
     p50_ms = None
-    if comm.rank == 0:
+    if args.full and comm.rank == 0:
         p50_ms = measure_submit_launch_p50(args.latency_samples)
 
     for _ in range(args.warmup):
@@ -143,6 +191,12 @@ def main() -> int:
         value = bus_bandwidth_gbps(payload_bytes, per_op, world)
     else:
         value = 2.0 * payload_bytes / per_op / 1e9
+
+    if args.dump_outputs and comm.rank == 0:
+        # the buffer a caller of the step holds afterwards: the reduced
+        # payload (identical on every rank) or, at N=1, the accumulator
+        dump_outputs(args.dump_outputs,
+                     {"allreduce_out": x} if world > 1 else {"reduce_out": y})
 
     if comm.rank == 0:
         out = {

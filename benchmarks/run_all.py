@@ -75,7 +75,7 @@ def main():
 
     section("allreduce_bench_py")
     subprocess.run([sys.executable, str(REPO / "bench.py"),
-                    "--steps", "50", "--warmup", "10"])
+                    "--steps", "50", "--warmup", "10", "--full"])
 
     section("rccl_binary")
     subprocess.run([str(REPO / "shipyard_amd" / "comm" /

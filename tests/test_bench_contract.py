@@ -15,7 +15,7 @@ REQUIRED = {"metric", "value", "unit", "n_gpus", "steps", "warmup",
 def test_bench_json_contract():
     out = subprocess.run(
         [sys.executable, str(REPO / "bench.py"), "--steps", "2",
-         "--warmup", "1", "--payload-mb", "4"],
+         "--warmup", "1", "--payload-mb", "4", "--full"],
         capture_output=True, text=True, timeout=300, cwd=str(REPO))
     assert out.returncode == 0, out.stderr[-500:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -34,6 +34,37 @@ def test_bench_json_contract():
     # p50 measured through the executor
     assert cfg["submit_launch_p50_ms"] is None or \
         cfg["submit_launch_p50_ms"] > 0
+
+
+def test_bench_plain_run_dumps_reproducible_outputs(tmp_path):
+    """A plain run (no --full) skips the executor latency measurement,
+    and --dump-outputs writes the last step's buffer as float32 .npy,
+    identical from run to run (seeded inputs)."""
+    import numpy as np
+
+    arrays = []
+    for name in ("a", "b"):
+        d = tmp_path / name
+        out = subprocess.run(
+            [sys.executable, str(REPO / "bench.py"), "--gpus", "1",
+             "--steps", "3", "--warmup", "1", "--payload-mb", "1",
+             "--dump-outputs", str(d)],
+            capture_output=True, text=True, timeout=300, cwd=str(REPO))
+        assert out.returncode == 0, out.stderr[-500:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, out.stdout
+        doc = json.loads(lines[0])
+        assert REQUIRED <= set(doc)
+        assert doc["steps"] == 3 and doc["ms_per_step"] > 0
+        assert doc["config"]["submit_launch_p50_ms"] is None
+        files = sorted(p.name for p in d.iterdir())
+        assert files == ["reduce_out.npy"]
+        arr = np.load(d / "reduce_out.npy")
+        assert arr.dtype == np.float32 and arr.ndim == 1
+        assert 0 < arr.nbytes <= 64 << 20
+        assert np.isfinite(arr).all() and arr.std() > 0
+        arrays.append(arr)
+    assert np.array_equal(arrays[0], arrays[1])
 
 
 def test_bench_world2_gloo_contract():
