@@ -22,22 +22,28 @@ from typing import Optional
 
 from . import gf2
 
-# device-side GF(2) operator cache: (kind, chunk, device) -> tensor
-# (the wrapper is called once per staged file; rebuilding the 32x32
-# operators host-side each call costs more than the kernel at 4 TB/s)
+# device-side GF(2) operator cache: (kind, chunk, n_chains, device) ->
+# tensor (the wrapper is called once per staged file; rebuilding the
+# 32x32 operators host-side each call costs more than the kernel at
+# 4 TB/s).  The v2 operator set has log2(256 * n_chains) levels of
+# shift-by-(chunk / (256 * n_chains)) * 2^k, so the chain count is part
+# of the key; the v3 set is geometry-fixed (n_chains == 0 there).
 _MAT_CACHE: dict = {}
 
 
-def _cached_mats(kind: str, chunk_size: int, device):
+def _cached_mats(kind: str, chunk_size: int, device, n_chains: int = 0):
     import torch
 
-    key = (kind, chunk_size, str(device))
+    if kind == "coal":
+        n_chains = 0
+    elif n_chains <= 0:
+        raise ValueError("v2 CRC operators need the launch's chain count")
+    key = (kind, chunk_size, n_chains, str(device))
     t = _MAT_CACHE.get(key)
     if t is None:
         if kind == "coal":
             vals = gf2.coalesced_matrices()
         else:
-            n_chains = gf2.pick_crc_chains(chunk_size)
             vals = gf2.level_matrices(chunk_size, 256 * n_chains)
         t = torch.tensor(vals, dtype=torch.int64).to(
             torch.uint32).to(device)
@@ -210,8 +216,9 @@ def crc32c_chunks(data, chunk_size: int = 256 * 1024, finish: bool = True):
         start = n_full if use_v3 else 0
         sub_n = n - start * chunk_size
         sub_chunks = n_chunks - start
+        # resolved once: the cached operators and the launch agree
         n_chains = gf2.pick_crc_chains(chunk_size)
-        d_mats = _cached_mats("v2", chunk_size, data.device)
+        d_mats = _cached_mats("v2", chunk_size, data.device, n_chains)
         rc = lib.sy_crc32c_chunks(
             ctypes.c_void_p(data.data_ptr() + start * chunk_size),
             ctypes.c_uint64(sub_n),

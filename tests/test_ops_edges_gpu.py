@@ -1,0 +1,389 @@
+"""GPU edge and dispatch-path tests for the HIP data-plane kernels.
+
+test_ops_gpu.py compares every kernel with its CPU reference at friendly
+shapes on the default dispatch path.  This module covers what that
+leaves open: grid-stride second trips, the multi-chain CRC
+instantiations, every LZ4 decoder geometry on both the single-wave and
+the producer/consumer kernel (with guard bytes around every output
+slot), the decoder's per-block error codes, the staged decoder path,
+the untested compressor instantiations and encoding edges, and SHA-256
+tail-page padding.  Every comparison is exact (bytes or integers)
+against gf2, lz4py or hashlib; inputs come from ops_edge_corpus.py and
+are seeded."""
+import hashlib
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+torch = pytest.importorskip("torch")
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import ops_edge_corpus as corpus  # noqa: E402
+
+from shipyard_amd.data import lz4py  # noqa: E402
+from shipyard_amd.ops import gf2  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+
+def _bytes(seed: int, n: int) -> np.ndarray:
+    return np.random.default_rng(seed).integers(0, 256, n, dtype=np.uint8)
+
+
+def _cuda(arr):
+    if isinstance(arr, (bytes, bytearray)):
+        arr = np.frombuffer(bytes(arr), dtype=np.uint8)
+    return torch.from_numpy(np.ascontiguousarray(arr).copy()).cuda()
+
+
+def _ints(t):
+    return [int(x) for x in t.tolist()]
+
+
+# ------------------------------------------------------------------ CRC32C
+class TestCrcEdges:
+    def test_v2_beyond_grid_cap(self):
+        """514 chunks on a 512-workgroup grid: workgroups 0 and 1 take a
+        second trip through the chunk loop and reuse lane_crc."""
+        from shipyard_amd import ops
+
+        chunk, n = 4096, 513 * 4096 + 7
+        host = _bytes(101, n)
+        d = _cuda(host)
+        got = _ints(ops.crc32c_chunks(d, chunk_size=chunk))
+        want = [int(w) for w in
+                gf2.crc32c_chunks_numpy(host.tobytes(), chunk)]
+        assert len(got) == 514
+        assert got == want
+        assert ops.crc32c_file_digest(d, chunk_size=chunk) == \
+            gf2.crc32c(host.tobytes())
+
+    def test_v3_beyond_grid_cap(self):
+        """1025 full chunks on the 1024-workgroup v3 grid (workgroup 0
+        reuses tiles[] / wave_crc) plus a 1-byte v2 tail chunk."""
+        from shipyard_amd import ops
+
+        chunk, n = 32768, 1025 * 32768 + 1
+        host = _bytes(102, n)
+        got = _ints(ops.crc32c_chunks(_cuda(host), chunk_size=chunk))
+        want = [int(w) for w in
+                gf2.crc32c_chunks_numpy(host.tobytes(), chunk)]
+        assert len(got) == 1026
+        assert got == want
+
+    @pytest.mark.parametrize("chunk", [32768, 65536, 98304])
+    def test_v3_chunk_sizes_raw(self, chunk):
+        """One, two and three 32 KiB rounds per chunk (98304 is not a
+        power of two), raw register values per chunk."""
+        from shipyard_amd import ops
+
+        host = _bytes(103 + chunk, 3 * chunk)
+        got = _ints(ops.crc32c_chunks_coal_raw(_cuda(host),
+                                               chunk_size=chunk))
+        want = [gf2.crc32c_raw(host[c * chunk:(c + 1) * chunk].tobytes())
+                for c in range(3)]
+        assert got == want
+
+    @pytest.mark.parametrize("chunk", [4096, 32768])
+    def test_ragged_tails_through_wrapper(self, chunk):
+        from shipyard_amd import ops
+
+        host = _bytes(104, 3 * chunk)
+        for n in (1, 15, 16, 17, chunk - 1, chunk + 1, 2 * chunk + 15,
+                  3 * chunk - 1):
+            data = host[:n]
+            got = _ints(ops.crc32c_chunks(_cuda(data), chunk_size=chunk))
+            want = [int(w) for w in
+                    gf2.crc32c_chunks_numpy(data.tobytes(), chunk)]
+            assert got == want, n
+
+    def test_multi_chain_in_one_process(self, monkeypatch):
+        """crc32c_chunks_kernel<2,9>, <4,10>, <8,11> and their
+        in-register pairwise combine.  The chain count changes inside one
+        process at one chunk size, so a matrix cache keyed without the
+        chain count would hand the 9..11-level kernels the 8-level
+        operator tensor cached by the first iteration."""
+        from shipyard_amd import ops
+
+        chunk = 32768
+        n = 3 * chunk + 777
+        host = _bytes(105, n)
+        d = _cuda(host)
+        want = [int(w) for w in
+                gf2.crc32c_chunks_numpy(host.tobytes(), chunk)]
+        monkeypatch.setenv("SHIPYARD_CRC_V3", "0")
+        for chains in (1, 2, 4, 8):
+            monkeypatch.setenv("SHIPYARD_CRC_CHAINS", str(chains))
+            got = _ints(ops.crc32c_chunks(d, chunk_size=chunk))
+            assert got == want, chains
+
+    @pytest.mark.parametrize("chunk", [4096, 32768])
+    def test_view_with_storage_offset(self, chunk):
+        from shipyard_amd import ops
+
+        buf = _cuda(_bytes(106, 4096 + 3 * chunk + 100))
+        view = buf[4096:]
+        assert view.storage_offset() == 4096 and view.data_ptr() % 16 == 0
+        a = ops.crc32c_chunks(view, chunk_size=chunk)
+        b = ops.crc32c_chunks(view.clone(), chunk_size=chunk)
+        assert _ints(a) == _ints(b)
+        host = view.cpu().numpy().tobytes()
+        assert _ints(a) == [int(w) for w in
+                            gf2.crc32c_chunks_numpy(host, chunk)]
+
+
+# ----------------------------------------------------------------- SHA-256
+def _sha_pages(host: np.ndarray, page: int) -> np.ndarray:
+    raw = host.tobytes()
+    ref = b"".join(hashlib.sha256(raw[o:o + page]).digest()
+                   for o in range(0, len(raw), page))
+    return np.frombuffer(ref, dtype=np.uint8).reshape(-1, 32)
+
+
+class TestShaEdges:
+    def test_beyond_grid_cap(self):
+        """524,292 pages on 2048 x 256 threads: threads 0..3 digest a
+        second page, the last of them the 57-byte tail page."""
+        from shipyard_amd import ops
+
+        n = 64 * 524288 + 64 * 3 + 57
+        host = _bytes(201, n)
+        got = ops.sha256_pages(_cuda(host), page_size=64).cpu().numpy()
+        want = _sha_pages(host, 64)
+        assert got.shape == want.shape == (524292, 32)
+        bad = np.nonzero((got != want).any(axis=1))[0]
+        assert bad.size == 0, "first differing page %d" % bad[0]
+
+    @pytest.mark.parametrize("page", [64, 192, 4096])
+    def test_tail_page_padding_behind_full_pages(self, page):
+        from shipyard_amd import ops
+
+        host = _bytes(202 + page, 4 * page)
+        for t in (1, 55, 56, 57, 63, 64, 65, 119, 120):
+            if t >= page:
+                continue
+            data = host[:3 * page + t]
+            got = ops.sha256_pages(_cuda(data), page_size=page)
+            got = got.cpu().numpy()
+            assert np.array_equal(got, _sha_pages(data, page)), t
+
+    def test_bad_page_size_is_rejected(self):
+        from shipyard_amd import ops
+
+        with pytest.raises(RuntimeError, match="-22"):
+            ops.sha256_pages(_cuda(_bytes(203, 400)), page_size=100)
+
+
+# -------------------------------------------------------------- LZ4 decode
+_RAW_CAPS = [4096, 8192, 16384, 32768, 65536]
+
+
+def _pc_effective_cap(raw_cap: int) -> int:
+    # sy_lz4_decode_blocks_pc has 8/16/64 KiB instantiations only
+    return 8192 if raw_cap <= 8192 else 16384 if raw_cap <= 16384 else 65536
+
+
+class TestLz4DecodeEdges:
+    @pytest.mark.parametrize("pc", [False, True])
+    @pytest.mark.parametrize("raw_cap", _RAW_CAPS)
+    def test_guarded_fuzz(self, raw_cap, pc):
+        """Every decoder geometry, slots at stride raw_cap + 64 in a
+        0xA5-filled tensor: payloads exact, every other byte untouched.
+        For pc the set holds a >200-sequence block (ring wrap, unbatched
+        tail publish)."""
+        corpus.check_guarded_fuzz(raw_cap, pc, seed=raw_cap + int(pc))
+
+    @pytest.mark.parametrize("pc", [False, True])
+    def test_error_codes_in_mixed_launch(self, pc):
+        """good, bad, good, bad, ... in one launch at raw_cap = 4096.
+
+        Expected codes are the table in ops_edge_corpus for both
+        kernels.  The producer of lz4_decode_pc_kernel runs the same
+        checks in the same order as lz4_decode_kernel: literal-length
+        TRUNC (producer loop `if (pos >= slen)` inside the litlen
+        extension), OVERFLOW (`dtotal + litlen > rawlen || pos + litlen
+        > slen`), offset TRUNC (`pos + 2 > slen`), match-length TRUNC,
+        OFFSET (`offset == 0 || offset > dtotal`), match OVERFLOW
+        (`dtotal + mlen > rawlen`) and MISMATCH once `pos == slen`.
+        Every check precedes the src read or dst write it guards, and
+        the consumer only executes records the producer has bounded.
+        One difference: pc has no 4 KiB instantiation, raw_cap = 4096
+        runs lz4_decode_pc_kernel<8192>, whose TOOBIG test is `rawlen >
+        8192`; the toobig case therefore claims 8193 bytes there, and
+        slots are spaced for the 8 KiB geometry."""
+        raw_cap = 4096
+        cap = _pc_effective_cap(raw_cap) if pc else raw_cap
+        bad = corpus.malformed_lz4_cases(cap)
+        rng_blocks = corpus.decode_fuzz_blocks(raw_cap, 31, many_seq=pc)
+        acc = corpus.accepted_lz4_case()
+        good = [(lz4py.compress_block(b), b) for b in rng_blocks]
+        good.insert(1, (acc[1], acc[3]))
+        streams, out_lens, expect, codes, names = [], [], [], [], []
+        for i, (name, stream, out_len, code) in enumerate(bad):
+            g_stream, g_raw = good[i % len(good)]
+            streams += [g_stream, stream]
+            out_lens += [len(g_raw), out_len]
+            expect += [g_raw, b""]
+            codes += [corpus.OK, code]
+            names += ["good", name]
+        streams.append(good[-1][0])
+        out_lens.append(len(good[-1][1]))
+        expect.append(good[-1][1])
+        codes.append(corpus.OK)
+        names.append("good")
+        status, got, stride = corpus.guarded_decode(
+            streams, out_lens, raw_cap, pc, stride=corpus.slot_stride(cap))
+        assert status == codes, [
+            (n, s, c) for n, s, c in zip(names, status, codes) if s != c]
+        corpus.check_slots(got, stride, expect)
+
+    @pytest.mark.parametrize("pc", [False, True])
+    def test_incompressible_64k_block(self, pc):
+        """in_len > out_len: the stream of a random 64 KiB block is
+        longer than the block (65 794 bytes, inside the staged kernels'
+        RAWCAP + 1024 - 48 limit)."""
+        raw = _bytes(301, 65536).tobytes()
+        stream = lz4py.compress_block(raw)
+        assert len(stream) > len(raw)
+        status, got, stride = corpus.guarded_decode(
+            [stream], [len(raw)], 65536, pc)
+        assert status == [corpus.OK]
+        corpus.check_slots(got, stride, [raw])
+
+    def test_staged_path_in_child_process(self):
+        """SY_LZ4_NOSTAGE is read once per process, so the staged v3
+        kernels (LDS-staged source, 16 B-aligned enclosing copy of an
+        unaligned stream) run in one fresh child interpreter."""
+        here = os.path.dirname(os.path.abspath(__file__))
+        root = os.path.dirname(here)
+        code = (
+            "import sys\n"
+            "sys.path[:0] = [%r, %r]\n"
+            "import ops_edge_corpus as c\n"
+            "c.check_guarded_fuzz(8192, False, 41)\n"
+            "c.check_guarded_fuzz(65536, False, 42)\n"
+            "print('OK')\n" % (here, root))
+        res = subprocess.run(
+            [sys.executable, "-c", code],
+            env={**os.environ, "SY_LZ4_NOSTAGE": "0"}, timeout=120,
+            capture_output=True, text=True)
+        assert res.returncode == 0, res.stdout + res.stderr
+        assert res.stdout.strip().splitlines()[-1] == "OK"
+
+
+# --------------------------------------------------------- GPU compressors
+def _gpu_compress(data: bytes, block_raw: int, screen: bool):
+    """-> (list of compressed bytes or None per block, device slots,
+    stride, lens)"""
+    from shipyard_amd import ops
+
+    d_out, stride, lens = ops.lz4_compress_blocks_gpu(
+        _cuda(data), block_raw, screen=screen)
+    torch.cuda.synchronize()
+    host = d_out.cpu().numpy()
+    lens_np = lens.numpy().view(np.uint32)
+    blobs = []
+    for b, ln in enumerate(int(x) for x in lens_np):
+        blobs.append(bytes(host[b * stride:b * stride + ln].tobytes())
+                     if ln else None)
+    return blobs, d_out, stride, lens_np
+
+
+def _raw_blocks(data: bytes, block_raw: int):
+    return [data[o:o + block_raw] for o in range(0, len(data), block_raw)]
+
+
+def _stored_size(blobs, raws):
+    return sum(len(c) if c is not None else len(r)
+               for c, r in zip(blobs, raws))
+
+
+def _seeded(seed: int, n: int) -> bytes:
+    import random
+
+    return corpus.mixed_content(random.Random(seed), n)
+
+
+class TestGpuCompressorEdges:
+    @pytest.mark.parametrize("block_raw", [16384, 32768])
+    def test_byte_identical_to_cpu(self, block_raw):
+        """lz4_compress_kernel<16 KiB> and <32 KiB>."""
+        from shipyard_amd import ops
+
+        data = _seeded(block_raw, block_raw * 5 + 1234)
+        cpu = ops.lz4_compress_blocks(data, block_raw)
+        blobs, _, _, _ = _gpu_compress(data, block_raw, screen=False)
+        assert len(blobs) == len(cpu) == 6
+        for b, (got, ref) in enumerate(zip(blobs, cpu)):
+            assert got == ref, b
+
+    @pytest.mark.parametrize("block_raw", [16384, 32768, 65536])
+    def test_screen_roundtrip_and_ratio(self, block_raw):
+        """lz4_compress_screen_kernel<16 KiB>, <32 KiB> and <64 KiB>."""
+        from shipyard_amd import ops
+
+        data = _seeded(block_raw + 1, block_raw * 4 + 1234)
+        raws = _raw_blocks(data, block_raw)
+        blobs, _, _, _ = _gpu_compress(data, block_raw, screen=True)
+        assert len(blobs) == len(raws)
+        for b, (blob, raw) in enumerate(zip(blobs, raws)):
+            if blob is None:
+                continue
+            assert len(blob) < len(raw), b
+            assert lz4py.decompress_block(blob, len(raw)) == raw, b
+        comp_v2 = _stored_size(blobs, raws)
+        comp_v1 = _stored_size(ops.lz4_compress_blocks(data, block_raw),
+                               raws)
+        # bound taken from TestScreenCompressor.test_roundtrip_and_ratio
+        assert comp_v2 <= comp_v1 * 1.25 + 1024, (comp_v1, comp_v2)
+
+    @pytest.mark.parametrize("screen", [False, True])
+    def test_encoding_edges(self, screen):
+        """Length-extension bytes of exactly 0, literal runs around the
+        15 and 270 thresholds, final blocks around the 13-byte minimum
+        and an input that is an exact block multiple, at block_raw =
+        4096: valid for lz4py and for the GPU decoder, and for the
+        greedy matcher byte-identical to the CPU compressor."""
+        from shipyard_amd import ops
+
+        block_raw = 4096
+        for name, data in corpus.compress_edge_blocks(block_raw):
+            raws = _raw_blocks(data, block_raw)
+            blobs, d_out, stride, lens = _gpu_compress(
+                data, block_raw, screen)
+            assert len(blobs) == len(raws), name
+            if not screen:
+                assert blobs == ops.lz4_compress_blocks(data, block_raw), \
+                    name
+            if name in ("final_5", "final_12"):
+                assert int(lens[-1]) == 0, name
+            kept = []
+            for b, (blob, raw) in enumerate(zip(blobs, raws)):
+                assert int(lens[b]) < len(raw), (name, b)
+                if blob is None:
+                    continue
+                assert lz4py.decompress_block(blob, len(raw)) == raw, \
+                    (name, b)
+                kept.append(b)
+            # decode the device-side slots in place on the GPU
+            dev = d_out.device
+            slot = corpus.slot_stride(block_raw)
+            out = torch.full((len(kept) * slot,), corpus.GUARD,
+                             dtype=torch.uint8, device=dev)
+            t64 = lambda v: torch.tensor(v, dtype=torch.int64, device=dev)
+            t32 = lambda v: torch.tensor(v, dtype=torch.int64).to(
+                torch.uint32).to(dev)
+            status = ops.lz4_decode_blocks(
+                d_out, t64([b * stride for b in kept]),
+                t32([int(lens[b]) for b in kept]), out,
+                t64([i * slot for i in range(len(kept))]),
+                t32([len(raws[b]) for b in kept]), raw_cap=block_raw,
+                pc=False)
+            torch.cuda.synchronize()
+            assert ops.lz4_all_ok(status), (name, status.cpu())
+            corpus.check_slots(out.cpu().numpy(), slot,
+                               [raws[b] for b in kept])
