@@ -39,6 +39,13 @@ ENTRY = struct.Struct("<QIII")
 # CRC chunk math requires >= 4 KiB and the block size to be 4 KiB-
 # aligned.  Compression-window loss vs 64 KiB is a few percent.
 DEFAULT_BLOCK_RAW = 8 * 1024
+# GPU geometry limits (validate_index / pack_gpu): the v2 CRC kernel
+# needs chunk_size % 4096 == 0 (sy_crc32c_chunks), which also keeps
+# every raw offset 16 B aligned for the uint4 stores; the LZ4 kernels
+# hold one block in LDS / u16 hash positions, so compressed blocks stop
+# at 64 KiB.
+GPU_BLOCK_ALIGN = 4096
+GPU_LZ4_BLOCK_MAX = 64 * 1024
 
 
 @dataclass
@@ -191,13 +198,27 @@ def pack(data: bytes, block_raw: int = DEFAULT_BLOCK_RAW,
     return hdr + table + payload.getvalue()
 
 
+def gpu_block_raw_ok(block_raw: int) -> bool:
+    """True when the GPU writer can author shards at this block size."""
+    return (0 < block_raw <= GPU_LZ4_BLOCK_MAX
+            and block_raw % GPU_BLOCK_ALIGN == 0)
+
+
 def pack_gpu(data, block_raw: int = DEFAULT_BLOCK_RAW) -> bytes:
     """GPU SYSHARD writer: block compression (ops GPU matcher) +
     per-block CRC32C both run on the MI355X; the host only assembles
     header/table around the copied-back payload.  ``data``: bytes or a
     uint8 CUDA tensor.  Default matcher is the wave-screen (v2);
     SHIPYARD_LZ4C_SCREEN=0 selects the serial-greedy matcher whose
-    output is bit-identical to the CPU ``pack()``."""
+    output is bit-identical to the CPU ``pack()``.
+
+    ``block_raw`` must be a multiple of 4096 and at most 65536
+    (ValueError otherwise, before anything touches the device); the CPU
+    ``pack()`` takes any block size."""
+    if not gpu_block_raw_ok(block_raw):
+        raise ValueError(
+            f"pack_gpu: block_raw={block_raw} must be a multiple of "
+            f"{GPU_BLOCK_ALIGN} and at most {GPU_LZ4_BLOCK_MAX}")
     import numpy as np
     import torch
 
@@ -292,8 +313,9 @@ def pack_auto(data: bytes, block_raw: int = DEFAULT_BLOCK_RAW,
     decodes; with SHIPYARD_LZ4C_SCREEN=0 the GPU matcher emits the
     CPU matcher's exact bytes (the default wave-screen matcher is
     ~equal ratio but not bit-identical — decode-side parity measured
-    in profiles/data_plane_r02.md)."""
-    if len(data) >= gpu_threshold:
+    in profiles/data_plane_r02.md).  Block sizes the GPU writer cannot
+    handle (see ``pack_gpu``) always take the CPU writer."""
+    if len(data) >= gpu_threshold and gpu_block_raw_ok(block_raw):
         try:
             import torch
 
@@ -308,14 +330,92 @@ def pack_auto(data: bytes, block_raw: int = DEFAULT_BLOCK_RAW,
 def read_index(buf: bytes) -> ShardIndex:
     import numpy as np
 
+    if len(buf) < HEADER.size:
+        raise ValueError("buffer shorter than the SYSHARD header")
     magic, flags, block_raw, raw_size, n_blocks = HEADER.unpack_from(buf, 0)
     if magic != MAGIC:
         raise ValueError("not a SYSHARD file")
+    if len(buf) - HEADER.size < n_blocks * ENTRY.size:
+        raise ValueError("buffer shorter than the SYSHARD block table")
     table = np.frombuffer(buf, dtype=_entry_dt(), count=n_blocks,
                           offset=HEADER.size)
     return ShardIndex(block_raw=block_raw, raw_size=raw_size,
                       payload_off=HEADER.size + n_blocks * ENTRY.size,
                       table=table)
+
+
+def validate_index(idx: ShardIndex, payload_len: int,
+                   for_gpu: bool = True) -> None:
+    """Check a block table against the format rules before any of its
+    numbers is used as an offset.  Raises ValueError naming the rule.
+
+    The table arrives from an object store or a peer; the GPU reader
+    hands comp_off/comp_len/raw_len straight to kernels as device
+    offsets, so every rule here is a bounds or alignment precondition of
+    gather_copy / lz4_decode_blocks / crc32c_chunks:
+
+    * n_blocks == ceil(raw_size / block_raw) (0 blocks iff raw_size 0)
+    * raw_len == block_raw except the last block (1..block_raw)
+    * sum(raw_len) == raw_size
+    * 1 <= comp_len <= raw_len
+    * comp_off % 16 == 0
+    * comp_off + comp_len <= payload_len (no uint64 wrap)
+    * for_gpu: block_raw % 4096 == 0, and block_raw <= 65536 when any
+      block is compressed (stored-only shards may use larger blocks)
+
+    O(n_blocks) vectorized numpy; ``unpack_cpu`` stays permissive and
+    does not call this."""
+    import numpy as np
+
+    t = idx.table
+    n = len(t)
+    block_raw = int(idx.block_raw)
+    raw_size = int(idx.raw_size)
+    payload_len = int(payload_len)
+    if block_raw <= 0:
+        raise ValueError("shard index: block_raw must be positive")
+    want = (raw_size + block_raw - 1) // block_raw
+    if n != want:
+        raise ValueError(
+            f"shard index: n_blocks={n} but ceil(raw_size/block_raw)="
+            f"{want} (raw_size={raw_size}, block_raw={block_raw})")
+    if for_gpu and block_raw % GPU_BLOCK_ALIGN:
+        raise ValueError(
+            f"shard index: block_raw={block_raw} is not a multiple of "
+            f"{GPU_BLOCK_ALIGN} (GPU reader)")
+    if n == 0:
+        return
+    raw_len = t["raw_len"]
+    comp_len = t["comp_len"]
+    comp_off = t["comp_off"]
+    if (raw_len[:-1] != block_raw).any():
+        raise ValueError("shard index: inner block raw_len != block_raw")
+    if not 1 <= int(raw_len[-1]) <= block_raw:
+        raise ValueError(
+            f"shard index: final raw_len={int(raw_len[-1])} outside "
+            f"1..{block_raw}")
+    total = int(raw_len.sum(dtype=np.uint64))
+    if total != raw_size:
+        raise ValueError(
+            f"shard index: sum(raw_len)={total} != raw_size={raw_size}")
+    if (comp_len == 0).any() or (comp_len > raw_len).any():
+        raise ValueError("shard index: comp_len outside 1..raw_len")
+    if (comp_off & np.uint64(15)).any():
+        raise ValueError("shard index: comp_off not 16-byte aligned")
+    # comp_off + comp_len <= payload_len without forming the uint64 sum
+    # (a comp_off near 2^64 would wrap it): compare the room behind
+    # each offset instead
+    plen = np.uint64(payload_len)
+    room = plen - np.minimum(comp_off, plen)
+    if (comp_off > plen).any() or (comp_len > room).any():
+        raise ValueError(
+            "shard index: comp_off + comp_len beyond the payload "
+            f"({payload_len} bytes; truncated or corrupt)")
+    if for_gpu and block_raw > GPU_LZ4_BLOCK_MAX \
+            and (comp_len != raw_len).any():
+        raise ValueError(
+            f"shard index: block_raw={block_raw} > {GPU_LZ4_BLOCK_MAX} "
+            "with compressed blocks (GPU reader)")
 
 
 def unpack_cpu(buf: bytes, verify: bool = True) -> bytes:
@@ -380,7 +480,13 @@ def decode_device(d_comp, idx: ShardIndex, device, verify: bool = True):
     """Decode an uploaded shard payload in HBM: batched gather-copy for
     stored blocks + wave-cooperative LZ4 for compressed ones + chunked
     CRC verify.  All host work is vectorized (numpy column arrays) —
-    O(1) python regardless of block count."""
+    O(1) python regardless of block count.
+
+    The table is validated first (``validate_index`` against
+    ``d_comp.numel()``): a bad table raises ValueError before a tensor
+    is made or a kernel launched."""
+    validate_index(idx, d_comp.numel(), for_gpu=True)
+
     import numpy as np
     import torch
 
@@ -441,7 +547,11 @@ def unpack_gpu(buf: bytes, device=None, verify: bool = True):
     dev = device or torch.device("cuda", torch.cuda.current_device())
     idx = read_index(buf)
     payload = buf[idx.payload_off:]
-    if not payload:  # empty shard: frombuffer rejects 0-length buffers
+    if not payload:
+        # frombuffer rejects 0-length buffers.  Only the empty shard may
+        # have no payload: a shard cut at the end of its table raises
+        # here instead of coming back as an empty tensor.
+        validate_index(idx, 0, for_gpu=True)
         return torch.empty(0, dtype=torch.uint8, device=dev)
     d_comp = torch.frombuffer(bytearray(payload), dtype=torch.uint8).to(
         dev, non_blocking=True)

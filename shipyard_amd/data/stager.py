@@ -129,9 +129,19 @@ class ShardStager:
                 sec = time.perf_counter() - t0
                 return out, StageResult(str(p), size, size, sec,
                                         decoded=False, verified=False)
+            if len(head) < shardfmt.HEADER.size:
+                raise ValueError(
+                    f"{p}: truncated inside the SYSHARD header")
             _, flags, block_raw, raw_size, n_blocks = \
                 shardfmt.HEADER.unpack(head)
-            table = f.read(shardfmt.ENTRY.size * n_blocks)
+            table_bytes = shardfmt.ENTRY.size * n_blocks
+            if size - shardfmt.HEADER.size < table_bytes:
+                raise ValueError(
+                    f"{p}: truncated inside the SYSHARD block table")
+            table = f.read(table_bytes)
+            if len(table) != table_bytes:
+                raise ValueError(
+                    f"{p}: truncated inside the SYSHARD block table")
             payload_total = size - shardfmt.HEADER.size - len(table)
             if self.native:
                 d_payload = self._upload_native(p, f.tell(), payload_total)
@@ -145,7 +155,9 @@ class ShardStager:
             block_raw=block_raw, raw_size=raw_size, payload_off=0,
             table=np.frombuffer(table, dtype=shardfmt._entry_dt(),
                                 count=n_blocks))
-        out = self._decode(d_payload, idx)
+        # the upload buffer is at least 1 byte; hand the decoder the true
+        # payload length so validate_index bounds the table against it
+        out = self._decode(d_payload[:payload_total], idx)
         sec = time.perf_counter() - t0
         res = StageResult(str(p), size, raw_size, sec, decoded=True,
                           verified=self.verify)

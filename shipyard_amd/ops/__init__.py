@@ -155,15 +155,36 @@ def _check(rc: int, what: str) -> None:
         raise RuntimeError(f"{what} failed with code {rc}")
 
 
+def _check_u8_device(t, what: str) -> None:
+    """Input contract of the kernels that walk a tensor with uint4
+    accesses from its base: uint8, contiguous, CUDA, and a base pointer
+    that is 16-byte aligned.  A contiguous view such as ``buf[1:]``
+    meets everything but the last and would fault or tear on the
+    device, so misalignment is a ValueError raised before any launch
+    (checked ahead of the device assert so the rule is testable on
+    hosts without a GPU)."""
+    import torch
+
+    assert t.dtype == torch.uint8 and t.is_contiguous(), what
+    if t.data_ptr() % 16:
+        raise ValueError(
+            f"{what}: base pointer must be 16-byte aligned (tensor "
+            f"storage offset {t.storage_offset()}); pass an aligned "
+            "view or .clone() it")
+    assert t.is_cuda, what
+
+
 def crc32c_chunks_coal_raw(data, chunk_size: int = 256 * 1024):
     """v3 coalesced-tile CRC kernel (experimental): RAW per-chunk CRCs
     for a tensor whose length is an exact multiple of chunk_size
-    (chunk_size % 32768 == 0).  See crc32c.hip v3 notes."""
+    (chunk_size % 32768 == 0).  See crc32c.hip v3 notes.
+
+    ``data``: contiguous uint8 CUDA tensor whose base pointer is
+    16-byte aligned (ValueError otherwise, before launch)."""
     import torch
 
+    _check_u8_device(data, "crc32c_chunks_coal_raw")
     lib = _load()
-    assert data.dtype == torch.uint8 and data.is_cuda \
-        and data.is_contiguous()
     n = data.numel()
     if chunk_size % 32768 or n % chunk_size:
         raise ValueError("coalesced CRC needs chunk%32768==0 and "
@@ -187,11 +208,15 @@ def crc32c_chunks(data, chunk_size: int = 256 * 1024, finish: bool = True):
     Returns a CPU torch.uint32 tensor of per-chunk CRCs (standard
     init/final-xor applied when ``finish``).  MI355X-native replacement
     for the reference's CPU-side file hashing (convoy/util.py:461-508).
+
+    ``data`` must be contiguous with a 16-byte-aligned base pointer
+    (both kernels load uint4 from the base); a misaligned view raises
+    ValueError before launch.
     """
     import torch
 
+    _check_u8_device(data, "crc32c_chunks")
     lib = _load()
-    assert data.dtype == torch.uint8 and data.is_cuda and data.is_contiguous()
     n = data.numel()
     n_chunks = (n + chunk_size - 1) // chunk_size
     out = torch.empty(n_chunks, dtype=torch.uint32, device=data.device)
@@ -276,15 +301,16 @@ def lz4_compress_blocks_gpu(data, block_raw: int,
     real-world shards).  ``data``
     is a uint8 CUDA tensor; returns (slotted uint8 CUDA tensor,
     stride, uint32 lens CPU tensor) — lens[b] == 0 means
-    incompressible (store raw)."""
+    incompressible (store raw).  The staging loop loads uint4 from
+    ``data``'s base: it must be contiguous and 16-byte aligned
+    (ValueError before launch otherwise)."""
     if screen is None:
         screen = _os.environ.get("SHIPYARD_LZ4C_SCREEN", "1") == "1"
 
     import torch
 
+    _check_u8_device(data, "lz4_compress_blocks_gpu")
     lib = _load()
-    assert data.dtype == torch.uint8 and data.is_cuda \
-        and data.is_contiguous()
     n = data.numel()
     n_blocks = (n + block_raw - 1) // block_raw
     if n_blocks == 0:
@@ -369,6 +395,24 @@ def gather_copy(src, src_off, dst, dst_off, lens):
     _check(rc, "sy_gather_copy")
 
 
+def _env_atoi(name: str, default: int) -> int:
+    """The value lz4_decode.hip's getenv + atoi gives for ``name``."""
+    e = _os.environ.get(name)
+    if e is None:
+        return default
+    try:
+        return int(e)
+    except ValueError:
+        return 0
+
+
+def _lz4_staged_by_env() -> bool:
+    """True when the environment sends sy_lz4_decode_blocks to a kernel
+    instantiation that stages the stream with uint4 loads (STAGE=1)."""
+    return _env_atoi("SY_LZ4_NOSTAGE", 1) == 0 or \
+        _env_atoi("SY_LZ4_SKIP", 0) in (1, 2)
+
+
 def lz4_decode_blocks(comp, in_off, in_len, out, out_off, out_len,
                       raw_cap: int = 64 * 1024, pc: bool = None):
     """Decode independent LZ4 blocks on the GPU.
@@ -379,14 +423,33 @@ def lz4_decode_blocks(comp, in_off, in_len, out, out_off, out_len,
     geometry: smaller blocks -> more workgroups/CU -> more latency
     hiding; the decoder is serial per block).  Returns a CUDA uint32
     status tensor (0 == OK per block).
+
+    ``out``'s base pointer must be 16-byte aligned (the decoded block
+    is streamed out with uint4 stores at ``out + out_off``); a
+    misaligned view raises ValueError before launch.  ``in_off`` may
+    always be unaligned.  ``comp``'s base may be unaligned only on the
+    default path, which parses the stream bytewise; the producer/
+    consumer path (``pc``) and the staged path (SY_LZ4_NOSTAGE=0, and
+    the SY_LZ4_SKIP probes) round the *offset* down to 16 and load
+    uint4 from ``comp + offset``, so there a misaligned ``comp`` base
+    raises ValueError before launch as well.
     """
     import os as _os
 
     import torch
 
-    lib = _load()
+    if out.data_ptr() % 16:
+        raise ValueError(
+            "lz4_decode_blocks: out base pointer must be 16-byte "
+            f"aligned (tensor storage offset {out.storage_offset()})")
     if pc is None:
         pc = _os.environ.get("SHIPYARD_LZ4_PC", "0") == "1"
+    if comp.data_ptr() % 16 and (pc or _lz4_staged_by_env()):
+        raise ValueError(
+            "lz4_decode_blocks: comp base pointer must be 16-byte "
+            "aligned on the producer/consumer and staged paths (tensor "
+            f"storage offset {comp.storage_offset()})")
+    lib = _load()
     fn = lib.sy_lz4_decode_blocks_pc if pc else lib.sy_lz4_decode_blocks
     n_blocks = in_off.numel()
     status = torch.empty(n_blocks, dtype=torch.uint32, device=comp.device)
@@ -409,11 +472,15 @@ def lz4_all_ok(status) -> bool:
 
 
 def sha256_pages(data, page_size: int = 4096):
-    """SHA-256 digest of each page of a uint8 CUDA tensor -> (n_pages, 32)."""
+    """SHA-256 digest of each page of a uint8 CUDA tensor -> (n_pages, 32).
+
+    ``data`` must be contiguous with a 16-byte-aligned base pointer
+    (message words are loaded as uint4); a misaligned view raises
+    ValueError before launch."""
     import torch
 
+    _check_u8_device(data, "sha256_pages")
     lib = _load()
-    assert data.dtype == torch.uint8 and data.is_cuda and data.is_contiguous()
     n = data.numel()
     n_pages = (n + page_size - 1) // page_size
     out = torch.empty((n_pages, 32), dtype=torch.uint8, device=data.device)

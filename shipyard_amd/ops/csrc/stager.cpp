@@ -138,9 +138,12 @@ SY_EXPORT int sy_stage_file(const char* path, void* d_dst,
     off += want;
     idx ^= 1;
   }
-  if (err == 0) {
+  // Drain the stream on the error path too: earlier windows' H2D
+  // copies may still be reading the ring, which the next call rewrites
+  // (or frees, when it grows) from its first pread on.
+  {
     hipError_t e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) err = (int)e;
+    if (e != hipSuccess && err == 0) err = (int)e;
   }
   if (out_seconds) {
     *out_seconds = std::chrono::duration<double>(

@@ -4,7 +4,9 @@ A plain helper module (not a conftest): every builder is seeded with
 ``random.Random(seed)`` so a failure reproduces byte for byte.  The
 CPU-only ``test_ops_edge_corpus.py`` pins that each builder really
 produces the encoding feature it is named for; ``test_ops_edges_gpu.py``
-feeds the same bytes to the kernels.
+feeds the same bytes to the kernels.  The shard corpus
+(``shard_corpus``) is pinned by ``test_shard_index_validation.py`` and
+drives ``test_shard_edges_gpu.py`` and the stager tests.
 """
 from __future__ import annotations
 
@@ -209,6 +211,68 @@ def compress_edge_blocks(block_raw: int) -> List[Tuple[str, bytes]]:
 def final_block(data: bytes, block_raw: int) -> bytes:
     n_blocks = (len(data) + block_raw - 1) // block_raw
     return data[(n_blocks - 1) * block_raw:]
+
+
+# ---------------------------------------------------------- shard corpora
+SHARD_BLOCK_SIZES = (4096, 8192, 16384, 32768, 65536)
+# final-block variant -> True when the writer must store it
+SHARD_FINALS = {
+    "equal_5": True,       # stored, < 16 B: gather_copy's byte tail only
+    "zeros_25": False,     # compressed 25-byte block
+    "random_bm1": True,    # stored, block_raw - 1 bytes (odd length)
+    "text_4k": False,      # compressed, 4001 bytes of text
+    "none": None,          # no final block: exact block multiple
+}
+SHARD_FULL_BLOCKS = 5      # text, random, byte run, random, mixed
+
+
+def shard_corpus(block_raw: int, final: str) -> bytes:
+    """Pipeline input for block size ``block_raw``: five full blocks
+    (text, random, a one-byte run, random, mixed) and the named final
+    block.  Blocks 1 and 3 are stored and blocks 0 and 2 compressed
+    under every writer; the five full blocks are the same for every
+    ``final`` of one block size."""
+    rng = random.Random(0x5A4D ^ block_raw)
+    blocks = [
+        text_like(rng, block_raw),
+        rng.randbytes(block_raw),
+        bytes([rng.randrange(256)]) * block_raw,
+        rng.randbytes(block_raw),
+        mixed_content(rng, block_raw),
+    ]
+    frng = random.Random(0xF1A1 ^ block_raw)
+    last = {
+        "equal_5": lambda: bytes([frng.randrange(256)]) * 5,
+        "zeros_25": lambda: b"\0" * 25,
+        "random_bm1": lambda: frng.randbytes(block_raw - 1),
+        "text_4k": lambda: text_like(frng, 4001),
+        "none": lambda: b"",
+    }[final]()
+    return b"".join(blocks) + last
+
+
+def shard_blocks(data: bytes, block_raw: int) -> List[bytes]:
+    return [data[o:o + block_raw] for o in range(0, len(data), block_raw)]
+
+
+def reversed_stored_shard(data: bytes, block_raw: int) -> bytes:
+    """Hand-built stored-only SYSHARD whose blocks sit in the payload in
+    reverse order: valid, but not the contiguous layout, so the GPU
+    reader must move every block with gather_copy."""
+    from shipyard_amd.data import shardfmt
+    from shipyard_amd.ops import gf2
+
+    blocks = shard_blocks(data, block_raw)
+    offs, payload = {}, bytearray()
+    for i in reversed(range(len(blocks))):
+        offs[i] = len(payload)
+        payload += blocks[i]
+        payload += b"\0" * (-len(payload) % 16)
+    table = b"".join(
+        shardfmt.ENTRY.pack(offs[i], len(b), len(b), gf2.crc32c(b))
+        for i, b in enumerate(blocks))
+    return (shardfmt.HEADER.pack(shardfmt.MAGIC, 0, block_raw, len(data),
+                                 len(blocks)) + table + bytes(payload))
 
 
 # ------------------------------------------------- guarded GPU decode run

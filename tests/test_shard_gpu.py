@@ -1,6 +1,5 @@
 """GPU test: SYSHARD unpack (LZ4 decode + CRC verify) on the MI355X
 vs the CPU reference reader."""
-import os
 import random
 
 import pytest
@@ -14,9 +13,9 @@ from shipyard_amd.data.integrity import compute_cpu, compute_gpu, verify  # noqa
 
 
 def test_unpack_gpu_matches_cpu():
-    random.seed(11)
-    data = (bytes(random.choices(b"abcdefgh", k=300_000)) +
-            os.urandom(150_000) + b"Z" * 90_000)
+    rng = random.Random(11)
+    data = (bytes(rng.choices(b"abcdefgh", k=300_000)) +
+            rng.randbytes(150_000) + b"Z" * 90_000)
     packed = shardfmt.pack(data)
     got = shardfmt.unpack_gpu(packed)
     torch.cuda.synchronize()
@@ -33,7 +32,7 @@ def test_unpack_gpu_detects_corruption():
 
 
 def test_gpu_manifest_matches_cpu():
-    data = os.urandom(2 * (1 << 20) + 777)
+    data = random.Random(12).randbytes(2 * (1 << 20) + 777)
     d = torch.frombuffer(bytearray(data), dtype=torch.uint8).to("cuda:0")
     m_gpu = compute_gpu(d, chunk_size=65536)
     m_cpu = compute_cpu(data, chunk_size=65536)

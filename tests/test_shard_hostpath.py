@@ -5,68 +5,17 @@ CPU.  The GPU numerics themselves are covered by tests/test_shard_gpu
 (-m gpu); this pins the host-side orchestration on every CPU run."""
 import os
 import random
-from unittest import mock
+import sys
 
 import pytest
 
 torch = pytest.importorskip("torch")
 
-from shipyard_amd.data import lz4py, shardfmt  # noqa: E402
-from shipyard_amd.ops import gf2  # noqa: E402
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+from shard_stub_ops import CpuOps, decode as _decode  # noqa: E402
 
-class CpuOps:
-    """Kernel emulation with the exact tensor contracts of ops.*"""
-
-    def __init__(self):
-        self.calls = []
-
-    def gather_copy(self, src, soff, dst, doff, lens):
-        assert soff.dtype == torch.int64 and doff.dtype == torch.int64
-        assert lens.dtype == torch.uint32
-        self.calls.append(("gather", soff.numel()))
-        for s, d, l in zip(soff.tolist(), doff.tolist(),
-                           lens.view(torch.int32).tolist()):
-            dst[d:d + l] = src[s:s + l]
-
-    def lz4_decode_blocks(self, comp, ioff, ilen, out, ooff, olen,
-                          raw_cap):
-        assert ioff.dtype == torch.int64 and ooff.dtype == torch.int64
-        assert ilen.dtype == torch.uint32 and olen.dtype == torch.uint32
-        self.calls.append(("lz4", ioff.numel()))
-        cb = bytes(comp.numpy().tobytes())
-        for io_, il, oo, ol in zip(
-                ioff.tolist(), ilen.view(torch.int32).tolist(),
-                ooff.tolist(), olen.view(torch.int32).tolist()):
-            raw = lz4py.decompress_block(cb[io_:io_ + il], ol)
-            out[oo:oo + ol] = torch.frombuffer(bytearray(raw),
-                                               dtype=torch.uint8)
-        return torch.zeros(ioff.numel(), dtype=torch.uint32)
-
-    @staticmethod
-    def lz4_all_ok(status):
-        return True
-
-    @staticmethod
-    def crc32c_chunks(t, chunk_size, n_chains=None):
-        b = bytes(t.numpy().tobytes())
-        return torch.tensor(
-            [gf2.crc32c(b[i:i + chunk_size])
-             for i in range(0, len(b), chunk_size)],
-            dtype=torch.int64).to(torch.uint32)
-
-
-def _decode(packed, fake):
-    idx = shardfmt.read_index(packed)
-    payload = bytearray(packed[idx.payload_off:]) or bytearray(1)
-    d_comp = torch.frombuffer(payload, dtype=torch.uint8)
-    with mock.patch("shipyard_amd.ops.gather_copy", fake.gather_copy), \
-         mock.patch("shipyard_amd.ops.lz4_decode_blocks",
-                    fake.lz4_decode_blocks), \
-         mock.patch("shipyard_amd.ops.lz4_all_ok", fake.lz4_all_ok), \
-         mock.patch("shipyard_amd.ops.crc32c_chunks", fake.crc32c_chunks):
-        out = shardfmt.decode_device(d_comp, idx, torch.device("cpu"))
-    return bytes(out.numpy().tobytes())
+from shipyard_amd.data import shardfmt  # noqa: E402
 
 
 def test_mixed_stored_and_lz4_blocks():
