@@ -9,7 +9,10 @@ the reference's reliance on dockerd gzip inflate + CPU MD5
 
 Layout (little-endian):
   8s  magic  b"SYSHARD1"
-  u32 flags            (bit0: blocks are LZ4; 0 = all stored)
+  u32 flags            (bit0: blocks are LZ4; 0 = all stored
+                        bit1: FILTER_SHUFFLE, blocks are byte-shuffled
+                        bits 8..15: shuffle element size E — 2, 4 or 8
+                        with bit1, 0 without; other bits ignored)
   u32 block_raw        (max raw bytes per block; 8 KiB default)
   u64 raw_size
   u32 n_blocks
@@ -19,6 +22,18 @@ Layout (little-endian):
 A block with comp_len == raw_len is STORED (incompressible); the GPU
 decoder copies it through.  comp offsets are relative to the payload
 start and 16 B aligned so uint4 paths stay aligned.
+
+FILTER_SHUFFLE (typed numeric shards: token ids, index arrays, float
+fields) byte-transposes every block before it is compressed or stored,
+the filter HDF5/Blosc/Zarr put in front of their codecs.  For a block
+of raw_len bytes, n_el = raw_len // E and body = n_el * E:
+
+  filtered[j*n_el + i] = raw[i*E + j]     0 <= j < E, 0 <= i < n_el
+  filtered[body:]      = raw[body:]       (raw_len % E leftover bytes)
+
+The per-block crc32c stays the CRC of the ORIGINAL bytes: integrity is
+end to end, and a reader that does not know the flag fails its CRC
+check instead of returning transposed data.
 """
 from __future__ import annotations
 
@@ -46,6 +61,78 @@ DEFAULT_BLOCK_RAW = 8 * 1024
 # at 64 KiB.
 GPU_BLOCK_ALIGN = 4096
 GPU_LZ4_BLOCK_MAX = 64 * 1024
+FLAG_LZ4 = 0x1
+FLAG_FILTER_SHUFFLE = 0x2
+SHUFFLE_ELEM_SHIFT = 8
+SHUFFLE_ELEM_SIZES = (2, 4, 8)
+
+
+def _check_shuffle_elem(shuffle_elem: int, what: str) -> int:
+    if shuffle_elem != 0 and shuffle_elem not in SHUFFLE_ELEM_SIZES:
+        raise ValueError(
+            f"{what}: shuffle_elem={shuffle_elem} must be 0 (no filter) "
+            f"or one of {SHUFFLE_ELEM_SIZES}")
+    return int(shuffle_elem)
+
+
+def shuffle_flags(shuffle_elem: int) -> int:
+    """The flags bits a writer sets for ``shuffle_elem`` (0 -> none)."""
+    if not shuffle_elem:
+        return 0
+    return FLAG_FILTER_SHUFFLE | (shuffle_elem << SHUFFLE_ELEM_SHIFT)
+
+
+def shuffle_elem_from_flags(flags: int) -> int:
+    """Element size of the shuffle filter named by a header's flags
+    word; 0 when FILTER_SHUFFLE is clear (the element-size bits are
+    then ignored like every other unknown bit).  ValueError when the
+    filter is on with an element size other than 2, 4 or 8."""
+    if not flags & FLAG_FILTER_SHUFFLE:
+        return 0
+    elem = (flags >> SHUFFLE_ELEM_SHIFT) & 0xFF
+    if elem not in SHUFFLE_ELEM_SIZES:
+        raise ValueError(
+            f"SYSHARD flags {flags:#x}: FILTER_SHUFFLE with element "
+            f"size {elem}, must be one of {SHUFFLE_ELEM_SIZES}")
+    return elem
+
+
+def shuffle_blocks_numpy(data, block_raw: int, elem_size: int,
+                         inverse: bool = False) -> bytes:
+    """Reference byte-shuffle of ``data`` laid out as ``block_raw``
+    blocks (the last may be short): per block, plane j holds byte j of
+    every ``elem_size``-byte element and the ``len % elem_size``
+    leftover is copied verbatim; ``inverse`` undoes it.  Vectorised:
+    one transpose for all full blocks, one for the ragged block.  The
+    CPU writer, the CPU reader and the tests of the device kernel
+    (ops.byte_shuffle) share it."""
+    import numpy as np
+
+    if elem_size not in SHUFFLE_ELEM_SIZES:
+        raise ValueError(f"elem_size={elem_size} not in {SHUFFLE_ELEM_SIZES}")
+    if block_raw <= 0:
+        raise ValueError("block_raw must be positive")
+    src = np.frombuffer(data, dtype=np.uint8)
+    out = np.empty_like(src)
+    n = len(src)
+    E = elem_size
+
+    def one(lo: int, n_blk: int, blk_len: int) -> None:
+        n_el = blk_len // E
+        body = n_el * E
+        s = src[lo:lo + n_blk * blk_len].reshape(n_blk, blk_len)
+        d = out[lo:lo + n_blk * blk_len].reshape(n_blk, blk_len)
+        shape = (n_blk, E, n_el) if inverse else (n_blk, n_el, E)
+        d[:, :body] = s[:, :body].reshape(shape).transpose(
+            0, 2, 1).reshape(n_blk, body)
+        d[:, body:] = s[:, body:]
+
+    n_full = n // block_raw
+    if n_full:
+        one(0, n_full, block_raw)
+    if n - n_full * block_raw:
+        one(n_full * block_raw, 1, n - n_full * block_raw)
+    return out.tobytes()
 
 
 @dataclass
@@ -78,15 +165,18 @@ class ShardIndex:
     """Parsed shard index.  The block table is held as numpy column
     arrays (comp_off/comp_len/raw_len/crc) so million-block shards
     decode without per-block python; `.blocks` materializes the
-    BlockEntry view lazily for tests/CPU paths."""
+    BlockEntry view lazily for tests/CPU paths.  ``shuffle_elem`` is
+    the FILTER_SHUFFLE element size (0: blocks are not filtered)."""
 
     def __init__(self, block_raw: int, raw_size: int, payload_off: int,
-                 table=None, blocks: List[BlockEntry] = None):
+                 table=None, blocks: List[BlockEntry] = None, *,
+                 shuffle_elem: int = 0):
         import numpy as np
 
         self.block_raw = block_raw
         self.raw_size = raw_size
         self.payload_off = payload_off
+        self.shuffle_elem = shuffle_elem
         if table is None:
             blocks = blocks or []
             table = np.zeros(len(blocks), dtype=_entry_dt())
@@ -135,14 +225,25 @@ def _compress_span(args):
 
 
 def pack(data: bytes, block_raw: int = DEFAULT_BLOCK_RAW,
-         compress: bool = True, workers: Optional[int] = None) -> bytes:
+         compress: bool = True, workers: Optional[int] = None,
+         shuffle_elem: int = 0) -> bytes:
     """Pack raw bytes into SYSHARD format (CPU writer).
+
+    `shuffle_elem` (2, 4 or 8; 0 = off) byte-shuffles every block over
+    elements of that size before it is compressed or stored
+    (FILTER_SHUFFLE, see the module docstring); the CRCs stay those of
+    the original bytes.
 
     `workers`: block compression is embarrassingly parallel (blocks are
     independent LZ4 streams); None = serial, 0 = one per CPU.  The
     replicator/mover pass workers=0 so layer packing scales with cores
     (the pure-python compressor does ~12 MB/s per core)."""
+    _check_shuffle_elem(shuffle_elem, "pack")
     crcs = gf2.crc32c_chunks_numpy(data, block_raw)
+    n_raw = len(data)
+    if shuffle_elem and data:
+        # from here on `data` is what the payload holds: filtered bytes
+        data = shuffle_blocks_numpy(data, block_raw, shuffle_elem)
     comps: List[bytes] = []
     if compress and data:
         # native multi-threaded compressor when the ops library is
@@ -184,15 +285,15 @@ def pack(data: bytes, block_raw: int = DEFAULT_BLOCK_RAW,
     payload = io.BytesIO()
     off = 0
     for bi, comp in enumerate(comps):
-        raw_len = min(block_raw, len(data) - bi * block_raw)
+        raw_len = min(block_raw, n_raw - bi * block_raw)
         crc = crcs[bi] if bi < len(crcs) else 0
         blocks.append(BlockEntry(off, len(comp), raw_len, crc))
         payload.write(comp)
         pad = _align16(len(comp)) - len(comp)
         payload.write(b"\x00" * pad)
         off += len(comp) + pad
-    hdr = HEADER.pack(MAGIC, 1 if compress else 0, block_raw, len(data),
-                      len(blocks))
+    flags = (FLAG_LZ4 if compress else 0) | shuffle_flags(shuffle_elem)
+    hdr = HEADER.pack(MAGIC, flags, block_raw, n_raw, len(blocks))
     table = b"".join(ENTRY.pack(b.comp_off, b.comp_len, b.raw_len, b.crc32c)
                      for b in blocks)
     return hdr + table + payload.getvalue()
@@ -204,7 +305,8 @@ def gpu_block_raw_ok(block_raw: int) -> bool:
             and block_raw % GPU_BLOCK_ALIGN == 0)
 
 
-def pack_gpu(data, block_raw: int = DEFAULT_BLOCK_RAW) -> bytes:
+def pack_gpu(data, block_raw: int = DEFAULT_BLOCK_RAW,
+             shuffle_elem: int = 0) -> bytes:
     """GPU SYSHARD writer: block compression (ops GPU matcher) +
     per-block CRC32C both run on the MI355X; the host only assembles
     header/table around the copied-back payload.  ``data``: bytes or a
@@ -214,11 +316,19 @@ def pack_gpu(data, block_raw: int = DEFAULT_BLOCK_RAW) -> bytes:
 
     ``block_raw`` must be a multiple of 4096 and at most 65536
     (ValueError otherwise, before anything touches the device); the CPU
-    ``pack()`` takes any block size."""
+    ``pack()`` takes any block size.
+
+    ``shuffle_elem`` (2, 4 or 8; 0 = off) applies FILTER_SHUFFLE: the
+    CRCs are taken from the original tensor, ops.byte_shuffle writes
+    the filtered copy (one more raw-sized buffer in HBM), and both the
+    matcher and the stored-block gather read that copy.  Output equals
+    ``pack(..., shuffle_elem=...)`` under the same matcher rule."""
     if not gpu_block_raw_ok(block_raw):
         raise ValueError(
             f"pack_gpu: block_raw={block_raw} must be a multiple of "
             f"{GPU_BLOCK_ALIGN} and at most {GPU_LZ4_BLOCK_MAX}")
+    _check_shuffle_elem(shuffle_elem, "pack_gpu")
+    flags = FLAG_LZ4 | shuffle_flags(shuffle_elem)
     import numpy as np
     import torch
 
@@ -241,10 +351,16 @@ def pack_gpu(data, block_raw: int = DEFAULT_BLOCK_RAW) -> bytes:
         n = t.numel()
         raw = None
     if n == 0:
-        return HEADER.pack(MAGIC, 1, block_raw, 0, 0)
+        return HEADER.pack(MAGIC, flags, block_raw, 0, 0)
     # device-side CRC of every block (raw_cap chunks; ragged tail ok)
     crcs = np.asarray(ops.crc32c_chunks(t, chunk_size=block_raw)
                       .numpy(), dtype=np.uint32)
+    if shuffle_elem:
+        # the payload holds filtered bytes; the CRCs above do not
+        t_raw = t
+        t = torch.empty_like(t_raw)
+        ops.byte_shuffle(t_raw, t, block_raw, shuffle_elem)
+        del t_raw
     d_out, stride, lens = ops.lz4_compress_blocks_gpu(t, block_raw)
     lens_np = lens.numpy().view(np.uint32)
     n_blocks = (n + block_raw - 1) // block_raw
@@ -299,14 +415,15 @@ def pack_gpu(data, block_raw: int = DEFAULT_BLOCK_RAW) -> bytes:
     table_arr["comp_len"] = comp_lens.astype(np.uint32)
     table_arr["raw_len"] = raw_lens
     table_arr["crc"] = crcs[:n_blocks]
-    hdr = HEADER.pack(MAGIC, 1, block_raw, n, n_blocks)
+    hdr = HEADER.pack(MAGIC, flags, block_raw, n, n_blocks)
     return b"".join((hdr, table_arr.tobytes(),
                      memoryview(pout.numpy())[:total]))
 
 
 def pack_auto(data: bytes, block_raw: int = DEFAULT_BLOCK_RAW,
               workers: Optional[int] = None,
-              gpu_threshold: int = 1 << 20) -> bytes:
+              gpu_threshold: int = 1 << 20,
+              shuffle_elem: int = 0) -> bytes:
     """Author a SYSHARD on the GPU when one is present and the
     payload is large enough to amortize the H2D hop; CPU writer
     otherwise.  Both outputs are valid shards that every reader
@@ -314,7 +431,9 @@ def pack_auto(data: bytes, block_raw: int = DEFAULT_BLOCK_RAW,
     CPU matcher's exact bytes (the default wave-screen matcher is
     ~equal ratio but not bit-identical — decode-side parity measured
     in profiles/data_plane_r02.md).  Block sizes the GPU writer cannot
-    handle (see ``pack_gpu``) always take the CPU writer."""
+    handle (see ``pack_gpu``) always take the CPU writer.
+    ``shuffle_elem`` goes to whichever writer is picked."""
+    _check_shuffle_elem(shuffle_elem, "pack_auto")
     if len(data) >= gpu_threshold and gpu_block_raw_ok(block_raw):
         try:
             import torch
@@ -323,8 +442,10 @@ def pack_auto(data: bytes, block_raw: int = DEFAULT_BLOCK_RAW,
         except Exception:
             use_gpu = False
         if use_gpu:
-            return pack_gpu(data, block_raw=block_raw)
-    return pack(data, block_raw=block_raw, workers=workers)
+            return pack_gpu(data, block_raw=block_raw,
+                            shuffle_elem=shuffle_elem)
+    return pack(data, block_raw=block_raw, workers=workers,
+                shuffle_elem=shuffle_elem)
 
 
 def read_index(buf: bytes) -> ShardIndex:
@@ -335,13 +456,14 @@ def read_index(buf: bytes) -> ShardIndex:
     magic, flags, block_raw, raw_size, n_blocks = HEADER.unpack_from(buf, 0)
     if magic != MAGIC:
         raise ValueError("not a SYSHARD file")
+    shuffle_elem = shuffle_elem_from_flags(flags)
     if len(buf) - HEADER.size < n_blocks * ENTRY.size:
         raise ValueError("buffer shorter than the SYSHARD block table")
     table = np.frombuffer(buf, dtype=_entry_dt(), count=n_blocks,
                           offset=HEADER.size)
     return ShardIndex(block_raw=block_raw, raw_size=raw_size,
                       payload_off=HEADER.size + n_blocks * ENTRY.size,
-                      table=table)
+                      table=table, shuffle_elem=shuffle_elem)
 
 
 def validate_index(idx: ShardIndex, payload_len: int,
@@ -362,6 +484,7 @@ def validate_index(idx: ShardIndex, payload_len: int,
     * comp_off + comp_len <= payload_len (no uint64 wrap)
     * for_gpu: block_raw % 4096 == 0, and block_raw <= 65536 when any
       block is compressed (stored-only shards may use larger blocks)
+    * shuffle_elem is 0, 2, 4 or 8 (ops.byte_shuffle takes no other)
 
     O(n_blocks) vectorized numpy; ``unpack_cpu`` stays permissive and
     does not call this."""
@@ -374,7 +497,8 @@ def validate_index(idx: ShardIndex, payload_len: int,
     payload_len = int(payload_len)
     if block_raw <= 0:
         raise ValueError("shard index: block_raw must be positive")
-    want = (raw_size + block_raw - 1) // block_raw
+    _check_shuffle_elem(getattr(idx, "shuffle_elem", 0), "shard index")
+    want =(raw_size + block_raw - 1) // block_raw
     if n != want:
         raise ValueError(
             f"shard index: n_blocks={n} but ceil(raw_size/block_raw)="
@@ -426,6 +550,10 @@ def unpack_cpu(buf: bytes, verify: bool = True) -> bytes:
         comp = buf[idx.payload_off + b.comp_off:
                    idx.payload_off + b.comp_off + b.comp_len]
         raw = comp if b.stored else lz4py.decompress_block(comp, b.raw_len)
+        if idx.shuffle_elem:
+            # one block per call: any block_raw >= raw_len keeps it whole
+            raw = shuffle_blocks_numpy(raw, max(len(raw), 1),
+                                       idx.shuffle_elem, inverse=True)
         if verify and gf2.crc32c(raw) != b.crc32c:
             raise ValueError("CRC mismatch in shard block")
         out.write(raw)
@@ -484,7 +612,15 @@ def decode_device(d_comp, idx: ShardIndex, device, verify: bool = True):
 
     The table is validated first (``validate_index`` against
     ``d_comp.numel()``): a bad table raises ValueError before a tensor
-    is made or a kernel launched."""
+    is made or a kernel launched.
+
+    FILTER_SHUFFLE shards (``idx.shuffle_elem``) decode into a scratch
+    buffer, ops.byte_shuffle(inverse) writes the output from it, and the
+    CRCs are taken over the output — the unfiltered bytes the table's
+    CRCs describe.  Peak HBM use for such a shard is 2x raw (scratch +
+    output) on top of the payload; the stored-contiguous fast path
+    unshuffles straight from the payload into a new tensor instead of
+    aliasing it.  ``d_comp``'s base must then be 16-byte aligned."""
     validate_index(idx, d_comp.numel(), for_gpu=True)
 
     import numpy as np
@@ -493,10 +629,15 @@ def decode_device(d_comp, idx: ShardIndex, device, verify: bool = True):
     from shipyard_amd import ops
 
     dev = device
+    shuffle_elem = idx.shuffle_elem
     if len(idx.table) == 0:
         return torch.empty(0, dtype=torch.uint8, device=dev)
     if _stored_contiguous(idx):
         out = d_comp[:idx.raw_size]
+        if shuffle_elem:
+            out = torch.empty(idx.raw_size, dtype=torch.uint8, device=dev)
+            ops.byte_shuffle(d_comp[:idx.raw_size], out, idx.block_raw,
+                             shuffle_elem, inverse=True)
         if verify:
             _verify_crcs_device(out, idx, dev)
         return out
@@ -505,6 +646,10 @@ def decode_device(d_comp, idx: ShardIndex, device, verify: bool = True):
     raw_offs = idx.raw_offs()
     stored = t["comp_len"] == t["raw_len"]
     out = torch.empty(max(idx.raw_size, 1), dtype=torch.uint8, device=dev)
+    if shuffle_elem:
+        # the kernels below fill `out`; keep that name on the scratch
+        # buffer and unshuffle into the real output afterwards
+        final = torch.empty_like(out)
 
     def to_dev(arr, dtype):
         return torch.from_numpy(np.ascontiguousarray(arr)).to(dev).view(
@@ -529,6 +674,10 @@ def decode_device(d_comp, idx: ShardIndex, device, verify: bool = True):
         if not ops.lz4_all_ok(status):
             raise ValueError(
                 f"GPU LZ4 decode failed: status={status.cpu().tolist()}")
+    if shuffle_elem:
+        ops.byte_shuffle(out[:idx.raw_size], final[:idx.raw_size],
+                         idx.block_raw, shuffle_elem, inverse=True)
+        out = final
     if verify:
         _verify_crcs_device(out, idx, dev)
     return out[:idx.raw_size]
@@ -559,8 +708,9 @@ def unpack_gpu(buf: bytes, device=None, verify: bool = True):
 
 
 def pack_file(src: Path, dst: Path, block_raw: int = DEFAULT_BLOCK_RAW,
-              compress: bool = True) -> ShardIndex:
+              compress: bool = True, shuffle_elem: int = 0) -> ShardIndex:
     data = Path(src).read_bytes()
-    packed = pack(data, block_raw=block_raw, compress=compress)
+    packed = pack(data, block_raw=block_raw, compress=compress,
+                  shuffle_elem=shuffle_elem)
     Path(dst).write_bytes(packed)
     return read_index(packed)

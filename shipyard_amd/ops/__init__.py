@@ -120,6 +120,11 @@ def _load() -> ctypes.CDLL:
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
     ]
+    lib.sy_byte_shuffle.restype = ctypes.c_int
+    lib.sy_byte_shuffle.argtypes = [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32,
+        ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p,
+    ]
     lib.sy_lz4_compress_blocks_gpu.restype = ctypes.c_int
     lib.sy_lz4_compress_blocks_gpu.argtypes = [
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
@@ -393,6 +398,65 @@ def gather_copy(src, src_off, dst, dst_off, lens):
         ctypes.c_void_p(dst_off.data_ptr()),
         ctypes.c_void_p(lens.data_ptr()), ctypes.c_uint32(n), _stream())
     _check(rc, "sy_gather_copy")
+
+
+SHUFFLE_ELEM_SIZES = (2, 4, 8)
+SHUFFLE_BLOCK_ALIGN = 4096
+
+
+def byte_shuffle(src, dst, block_raw: int, elem_size: int,
+                 inverse: bool = False):
+    """SYSHARD byte-shuffle filter on the device: ``dst`` receives
+    ``src`` with every ``block_raw`` block (the last one may be short)
+    byte-transposed over ``elem_size``-byte elements — plane j of a
+    block holds byte j of each of its elements, the ``len % elem_size``
+    leftover is copied verbatim.  ``inverse=True`` undoes it.  The byte
+    layout is ``shardfmt.shuffle_blocks_numpy``'s.
+
+    ``src``/``dst``: contiguous uint8 CUDA tensors of equal numel whose
+    base pointers are 16-byte aligned and whose byte ranges do not
+    overlap; ``elem_size`` in {2, 4, 8}; ``block_raw`` a positive
+    multiple of 4096 below 2**32.  Each violation is a ValueError raised
+    before any launch (and ahead of the device assert, so the rules are
+    testable on hosts without a GPU)."""
+    import torch
+
+    for t, name in ((src, "src"), (dst, "dst")):
+        assert t.dtype == torch.uint8 and t.is_contiguous(), \
+            f"byte_shuffle: {name}"
+        if t.data_ptr() % 16:
+            raise ValueError(
+                f"byte_shuffle: {name} base pointer must be 16-byte "
+                f"aligned (tensor storage offset {t.storage_offset()}); "
+                "pass an aligned view or .clone() it")
+    n = src.numel()
+    if dst.numel() != n:
+        raise ValueError(
+            f"byte_shuffle: src has {n} bytes but dst {dst.numel()}")
+    if n and src.data_ptr() < dst.data_ptr() + n and \
+            dst.data_ptr() < src.data_ptr() + n:
+        raise ValueError(
+            "byte_shuffle: src and dst overlap (the transpose cannot "
+            "run in place)")
+    if elem_size not in SHUFFLE_ELEM_SIZES:
+        raise ValueError(
+            f"byte_shuffle: elem_size={elem_size} not in "
+            f"{SHUFFLE_ELEM_SIZES}")
+    if not 0 < block_raw < (1 << 32) or block_raw % SHUFFLE_BLOCK_ALIGN:
+        raise ValueError(
+            f"byte_shuffle: block_raw={block_raw} must be a positive "
+            f"multiple of {SHUFFLE_BLOCK_ALIGN} below 2**32")
+    assert src.is_cuda and dst.is_cuda and src.device == dst.device, \
+        "byte_shuffle: CUDA tensors on one device"
+    if n == 0:
+        return
+    lib = _load()
+    rc = lib.sy_byte_shuffle(
+        ctypes.c_void_p(src.data_ptr()), ctypes.c_void_p(dst.data_ptr()),
+        ctypes.c_uint64(n), ctypes.c_uint32(block_raw),
+        ctypes.c_uint32(elem_size), ctypes.c_int(int(bool(inverse))),
+        _stream())
+    _check(rc, "sy_byte_shuffle")
 
 
 def _env_atoi(name: str, default: int) -> int:
