@@ -12,7 +12,10 @@ Layout (little-endian):
   u32 flags            (bit0: blocks are LZ4; 0 = all stored
                         bit1: FILTER_SHUFFLE, blocks are byte-shuffled
                         bits 8..15: shuffle element size E — 2, 4 or 8
-                        with bit1, 0 without; other bits ignored)
+                        with bit1, 0 without
+                        bit2: FILTER_DELTA, blocks hold element deltas
+                        bits 16..23: delta element size D — 2, 4 or 8
+                        with bit2, 0 without; other bits ignored)
   u32 block_raw        (max raw bytes per block; 8 KiB default)
   u64 raw_size
   u32 n_blocks
@@ -34,6 +37,26 @@ of raw_len bytes, n_el = raw_len // E and body = n_el * E:
 The per-block crc32c stays the CRC of the ORIGINAL bytes: integrity is
 end to end, and a reader that does not know the flag fails its CRC
 check instead of returning transposed data.
+
+FILTER_DELTA (monotone or slowly varying typed shards: document and
+sample offsets, CSR row pointers, sorted ids, timestamps) stores
+differences instead of values, the filter Zarr/numcodecs ``Delta`` and
+Blosc2 put in front of the shuffle.  For a block of raw_len bytes,
+n_el = raw_len // D; the elements are little-endian unsigned integers
+and all arithmetic is mod 2^(8*D):
+
+  d[0] = x[0]
+  d[i] = x[i] - x[i-1]                    1 <= i < n_el
+  filtered[n_el*D:] = raw[n_el*D:]        (raw_len % D leftover bytes)
+
+The running value restarts at every block, so blocks stay independently
+decodable.  Writers apply delta first, then shuffle if both are
+requested, then LZ4 or store; readers undo them in the reverse order.
+D and E are independent fields and need not be equal.  The per-block
+crc32c is again that of the ORIGINAL bytes.  The filter is opt-in per
+shard: data that is not monotone (uniform token ids) gets WORSE under
+delta, because differences of independent values are noisier than the
+values.
 """
 from __future__ import annotations
 
@@ -65,6 +88,9 @@ FLAG_LZ4 = 0x1
 FLAG_FILTER_SHUFFLE = 0x2
 SHUFFLE_ELEM_SHIFT = 8
 SHUFFLE_ELEM_SIZES = (2, 4, 8)
+FLAG_FILTER_DELTA = 0x4
+DELTA_ELEM_SHIFT = 16
+DELTA_ELEM_SIZES = (2, 4, 8)
 
 
 def _check_shuffle_elem(shuffle_elem: int, what: str) -> int:
@@ -94,6 +120,36 @@ def shuffle_elem_from_flags(flags: int) -> int:
         raise ValueError(
             f"SYSHARD flags {flags:#x}: FILTER_SHUFFLE with element "
             f"size {elem}, must be one of {SHUFFLE_ELEM_SIZES}")
+    return elem
+
+
+def _check_delta_elem(delta_elem: int, what: str) -> int:
+    if delta_elem != 0 and delta_elem not in DELTA_ELEM_SIZES:
+        raise ValueError(
+            f"{what}: delta_elem={delta_elem} must be 0 (no filter) "
+            f"or one of {DELTA_ELEM_SIZES}")
+    return int(delta_elem)
+
+
+def delta_flags(delta_elem: int) -> int:
+    """The flags bits a writer sets for ``delta_elem`` (0 -> none)."""
+    if not delta_elem:
+        return 0
+    return FLAG_FILTER_DELTA | (delta_elem << DELTA_ELEM_SHIFT)
+
+
+def delta_elem_from_flags(flags: int) -> int:
+    """Element size of the delta filter named by a header's flags word;
+    0 when FILTER_DELTA is clear (bits 16..23 are then ignored like
+    every other unknown bit).  ValueError when the filter is on with an
+    element size other than 2, 4 or 8."""
+    if not flags & FLAG_FILTER_DELTA:
+        return 0
+    elem = (flags >> DELTA_ELEM_SHIFT) & 0xFF
+    if elem not in DELTA_ELEM_SIZES:
+        raise ValueError(
+            f"SYSHARD flags {flags:#x}: FILTER_DELTA with element "
+            f"size {elem}, must be one of {DELTA_ELEM_SIZES}")
     return elem
 
 
@@ -135,6 +191,52 @@ def shuffle_blocks_numpy(data, block_raw: int, elem_size: int,
     return out.tobytes()
 
 
+def delta_blocks_numpy(data, block_raw: int, elem_size: int,
+                       inverse: bool = False) -> bytes:
+    """Reference delta filter of ``data`` laid out as ``block_raw``
+    blocks (the last may be short): per block, every ``elem_size``-byte
+    little-endian unsigned element but the first is replaced by its
+    difference to the one before it (mod 2**(8*elem_size)) and the
+    ``len % elem_size`` leftover is copied verbatim; ``inverse`` sums
+    the differences up again.  Vectorised: one shifted subtract (or one
+    ``np.cumsum`` in the unsigned dtype) for all full blocks, one for
+    the ragged block.  The CPU writer, the CPU reader and the tests of
+    the device kernel (ops.delta_filter) share it."""
+    import numpy as np
+
+    if elem_size not in DELTA_ELEM_SIZES:
+        raise ValueError(f"elem_size={elem_size} not in {DELTA_ELEM_SIZES}")
+    if block_raw <= 0:
+        raise ValueError("block_raw must be positive")
+    src = np.frombuffer(data, dtype=np.uint8)
+    out = np.empty_like(src)
+    n = len(src)
+    E = elem_size
+    dt = np.dtype(f"<u{E}")
+
+    def one(lo: int, n_blk: int, blk_len: int) -> None:
+        n_el = blk_len // E
+        body = n_el * E
+        s = src[lo:lo + n_blk * blk_len].reshape(n_blk, blk_len)
+        d = out[lo:lo + n_blk * blk_len].reshape(n_blk, blk_len)
+        if n_el:
+            x = np.ascontiguousarray(s[:, :body]).view(dt)
+            if inverse:
+                y = np.cumsum(x, axis=1, dtype=dt)
+            else:
+                y = x.copy()
+                y[:, 1:] -= x[:, :-1]
+            d[:, :body] = y.view(np.uint8)
+        d[:, body:] = s[:, body:]
+
+    n_full = n // block_raw
+    if n_full:
+        one(0, n_full, block_raw)
+    if n - n_full * block_raw:
+        one(n_full * block_raw, 1, n - n_full * block_raw)
+    return out.tobytes()
+
+
 @dataclass
 class BlockEntry:
     comp_off: int
@@ -166,17 +268,19 @@ class ShardIndex:
     arrays (comp_off/comp_len/raw_len/crc) so million-block shards
     decode without per-block python; `.blocks` materializes the
     BlockEntry view lazily for tests/CPU paths.  ``shuffle_elem`` is
-    the FILTER_SHUFFLE element size (0: blocks are not filtered)."""
+    the FILTER_SHUFFLE element size and ``delta_elem`` the FILTER_DELTA
+    one (0: that filter is off)."""
 
     def __init__(self, block_raw: int, raw_size: int, payload_off: int,
                  table=None, blocks: List[BlockEntry] = None, *,
-                 shuffle_elem: int = 0):
+                 shuffle_elem: int = 0, delta_elem: int = 0):
         import numpy as np
 
         self.block_raw = block_raw
         self.raw_size = raw_size
         self.payload_off = payload_off
         self.shuffle_elem = shuffle_elem
+        self.delta_elem = delta_elem
         if table is None:
             blocks = blocks or []
             table = np.zeros(len(blocks), dtype=_entry_dt())
@@ -226,7 +330,7 @@ def _compress_span(args):
 
 def pack(data: bytes, block_raw: int = DEFAULT_BLOCK_RAW,
          compress: bool = True, workers: Optional[int] = None,
-         shuffle_elem: int = 0) -> bytes:
+         shuffle_elem: int = 0, delta_elem: int = 0) -> bytes:
     """Pack raw bytes into SYSHARD format (CPU writer).
 
     `shuffle_elem` (2, 4 or 8; 0 = off) byte-shuffles every block over
@@ -234,13 +338,22 @@ def pack(data: bytes, block_raw: int = DEFAULT_BLOCK_RAW,
     (FILTER_SHUFFLE, see the module docstring); the CRCs stay those of
     the original bytes.
 
+    `delta_elem` (2, 4 or 8; 0 = off) first replaces the elements of
+    that size by their differences inside every block (FILTER_DELTA),
+    ahead of the shuffle; meant for monotone data such as offsets,
+    sorted ids and timestamps, and opt-in because it makes other data
+    compress worse.
+
     `workers`: block compression is embarrassingly parallel (blocks are
     independent LZ4 streams); None = serial, 0 = one per CPU.  The
     replicator/mover pass workers=0 so layer packing scales with cores
     (the pure-python compressor does ~12 MB/s per core)."""
     _check_shuffle_elem(shuffle_elem, "pack")
+    _check_delta_elem(delta_elem, "pack")
     crcs = gf2.crc32c_chunks_numpy(data, block_raw)
     n_raw = len(data)
+    if delta_elem and data:
+        data = delta_blocks_numpy(data, block_raw, delta_elem)
     if shuffle_elem and data:
         # from here on `data` is what the payload holds: filtered bytes
         data = shuffle_blocks_numpy(data, block_raw, shuffle_elem)
@@ -292,7 +405,8 @@ def pack(data: bytes, block_raw: int = DEFAULT_BLOCK_RAW,
         pad = _align16(len(comp)) - len(comp)
         payload.write(b"\x00" * pad)
         off += len(comp) + pad
-    flags = (FLAG_LZ4 if compress else 0) | shuffle_flags(shuffle_elem)
+    flags = (FLAG_LZ4 if compress else 0) | shuffle_flags(shuffle_elem) \
+        | delta_flags(delta_elem)
     hdr = HEADER.pack(MAGIC, flags, block_raw, n_raw, len(blocks))
     table = b"".join(ENTRY.pack(b.comp_off, b.comp_len, b.raw_len, b.crc32c)
                      for b in blocks)
@@ -306,7 +420,7 @@ def gpu_block_raw_ok(block_raw: int) -> bool:
 
 
 def pack_gpu(data, block_raw: int = DEFAULT_BLOCK_RAW,
-             shuffle_elem: int = 0) -> bytes:
+             shuffle_elem: int = 0, delta_elem: int = 0) -> bytes:
     """GPU SYSHARD writer: block compression (ops GPU matcher) +
     per-block CRC32C both run on the MI355X; the host only assembles
     header/table around the copied-back payload.  ``data``: bytes or a
@@ -322,13 +436,21 @@ def pack_gpu(data, block_raw: int = DEFAULT_BLOCK_RAW,
     CRCs are taken from the original tensor, ops.byte_shuffle writes
     the filtered copy (one more raw-sized buffer in HBM), and both the
     matcher and the stored-block gather read that copy.  Output equals
-    ``pack(..., shuffle_elem=...)`` under the same matcher rule."""
+    ``pack(..., shuffle_elem=...)`` under the same matcher rule.
+
+    ``delta_elem`` (2, 4 or 8; 0 = off) applies FILTER_DELTA ahead of
+    the shuffle: ops.delta_filter writes the differences into a new
+    buffer (a tensor passed in stays untouched), and with both filters
+    on ops.byte_shuffle reads that buffer, which is freed as soon as
+    the shuffled copy exists.  Output equals
+    ``pack(..., delta_elem=...)`` under the same matcher rule."""
     if not gpu_block_raw_ok(block_raw):
         raise ValueError(
             f"pack_gpu: block_raw={block_raw} must be a multiple of "
             f"{GPU_BLOCK_ALIGN} and at most {GPU_LZ4_BLOCK_MAX}")
     _check_shuffle_elem(shuffle_elem, "pack_gpu")
-    flags = FLAG_LZ4 | shuffle_flags(shuffle_elem)
+    _check_delta_elem(delta_elem, "pack_gpu")
+    flags = FLAG_LZ4 | shuffle_flags(shuffle_elem) | delta_flags(delta_elem)
     import numpy as np
     import torch
 
@@ -355,8 +477,13 @@ def pack_gpu(data, block_raw: int = DEFAULT_BLOCK_RAW,
     # device-side CRC of every block (raw_cap chunks; ragged tail ok)
     crcs = np.asarray(ops.crc32c_chunks(t, chunk_size=block_raw)
                       .numpy(), dtype=np.uint32)
-    if shuffle_elem:
+    if delta_elem:
         # the payload holds filtered bytes; the CRCs above do not
+        t_raw = t
+        t = torch.empty_like(t_raw)
+        ops.delta_filter(t_raw, t, block_raw, delta_elem)
+        del t_raw
+    if shuffle_elem:
         t_raw = t
         t = torch.empty_like(t_raw)
         ops.byte_shuffle(t_raw, t, block_raw, shuffle_elem)
@@ -423,7 +550,7 @@ def pack_gpu(data, block_raw: int = DEFAULT_BLOCK_RAW,
 def pack_auto(data: bytes, block_raw: int = DEFAULT_BLOCK_RAW,
               workers: Optional[int] = None,
               gpu_threshold: int = 1 << 20,
-              shuffle_elem: int = 0) -> bytes:
+              shuffle_elem: int = 0, delta_elem: int = 0) -> bytes:
     """Author a SYSHARD on the GPU when one is present and the
     payload is large enough to amortize the H2D hop; CPU writer
     otherwise.  Both outputs are valid shards that every reader
@@ -432,8 +559,10 @@ def pack_auto(data: bytes, block_raw: int = DEFAULT_BLOCK_RAW,
     ~equal ratio but not bit-identical — decode-side parity measured
     in profiles/data_plane_r02.md).  Block sizes the GPU writer cannot
     handle (see ``pack_gpu``) always take the CPU writer.
-    ``shuffle_elem`` goes to whichever writer is picked."""
+    ``shuffle_elem`` and ``delta_elem`` go to whichever writer is
+    picked."""
     _check_shuffle_elem(shuffle_elem, "pack_auto")
+    _check_delta_elem(delta_elem, "pack_auto")
     if len(data) >= gpu_threshold and gpu_block_raw_ok(block_raw):
         try:
             import torch
@@ -443,9 +572,10 @@ def pack_auto(data: bytes, block_raw: int = DEFAULT_BLOCK_RAW,
             use_gpu = False
         if use_gpu:
             return pack_gpu(data, block_raw=block_raw,
-                            shuffle_elem=shuffle_elem)
+                            shuffle_elem=shuffle_elem,
+                            delta_elem=delta_elem)
     return pack(data, block_raw=block_raw, workers=workers,
-                shuffle_elem=shuffle_elem)
+                shuffle_elem=shuffle_elem, delta_elem=delta_elem)
 
 
 def read_index(buf: bytes) -> ShardIndex:
@@ -457,13 +587,15 @@ def read_index(buf: bytes) -> ShardIndex:
     if magic != MAGIC:
         raise ValueError("not a SYSHARD file")
     shuffle_elem = shuffle_elem_from_flags(flags)
+    delta_elem = delta_elem_from_flags(flags)
     if len(buf) - HEADER.size < n_blocks * ENTRY.size:
         raise ValueError("buffer shorter than the SYSHARD block table")
     table = np.frombuffer(buf, dtype=_entry_dt(), count=n_blocks,
                           offset=HEADER.size)
     return ShardIndex(block_raw=block_raw, raw_size=raw_size,
                       payload_off=HEADER.size + n_blocks * ENTRY.size,
-                      table=table, shuffle_elem=shuffle_elem)
+                      table=table, shuffle_elem=shuffle_elem,
+                      delta_elem=delta_elem)
 
 
 def validate_index(idx: ShardIndex, payload_len: int,
@@ -485,6 +617,7 @@ def validate_index(idx: ShardIndex, payload_len: int,
     * for_gpu: block_raw % 4096 == 0, and block_raw <= 65536 when any
       block is compressed (stored-only shards may use larger blocks)
     * shuffle_elem is 0, 2, 4 or 8 (ops.byte_shuffle takes no other)
+    * delta_elem is 0, 2, 4 or 8 (ops.delta_filter takes no other)
 
     O(n_blocks) vectorized numpy; ``unpack_cpu`` stays permissive and
     does not call this."""
@@ -498,6 +631,7 @@ def validate_index(idx: ShardIndex, payload_len: int,
     if block_raw <= 0:
         raise ValueError("shard index: block_raw must be positive")
     _check_shuffle_elem(getattr(idx, "shuffle_elem", 0), "shard index")
+    _check_delta_elem(getattr(idx, "delta_elem", 0), "shard index")
     want =(raw_size + block_raw - 1) // block_raw
     if n != want:
         raise ValueError(
@@ -554,6 +688,9 @@ def unpack_cpu(buf: bytes, verify: bool = True) -> bytes:
             # one block per call: any block_raw >= raw_len keeps it whole
             raw = shuffle_blocks_numpy(raw, max(len(raw), 1),
                                        idx.shuffle_elem, inverse=True)
+        if idx.delta_elem:
+            raw = delta_blocks_numpy(raw, max(len(raw), 1),
+                                     idx.delta_elem, inverse=True)
         if verify and gf2.crc32c(raw) != b.crc32c:
             raise ValueError("CRC mismatch in shard block")
         out.write(raw)
@@ -620,7 +757,17 @@ def decode_device(d_comp, idx: ShardIndex, device, verify: bool = True):
     CRCs describe.  Peak HBM use for such a shard is 2x raw (scratch +
     output) on top of the payload; the stored-contiguous fast path
     unshuffles straight from the payload into a new tensor instead of
-    aliasing it.  ``d_comp``'s base must then be 16-byte aligned."""
+    aliasing it.  ``d_comp``'s base must then be 16-byte aligned.
+
+    FILTER_DELTA shards (``idx.delta_elem``) add one
+    ops.delta_filter(inverse) launch that runs IN PLACE on the output
+    tensor, after the unshuffle when both filters are on, and the CRCs
+    are taken after it.  So the peak stays what it was: 1x raw for
+    delta alone (the decode target is the output), 2x raw for delta +
+    shuffle.  On the stored-contiguous fast path with delta alone the
+    kernel reads the payload and writes a new tensor (1x raw), so the
+    payload is neither aliased nor modified; its base must be 16-byte
+    aligned there too."""
     validate_index(idx, d_comp.numel(), for_gpu=True)
 
     import numpy as np
@@ -630,6 +777,7 @@ def decode_device(d_comp, idx: ShardIndex, device, verify: bool = True):
 
     dev = device
     shuffle_elem = idx.shuffle_elem
+    delta_elem = idx.delta_elem
     if len(idx.table) == 0:
         return torch.empty(0, dtype=torch.uint8, device=dev)
     if _stored_contiguous(idx):
@@ -638,6 +786,13 @@ def decode_device(d_comp, idx: ShardIndex, device, verify: bool = True):
             out = torch.empty(idx.raw_size, dtype=torch.uint8, device=dev)
             ops.byte_shuffle(d_comp[:idx.raw_size], out, idx.block_raw,
                              shuffle_elem, inverse=True)
+            if delta_elem:
+                ops.delta_filter(out, out, idx.block_raw, delta_elem,
+                                 inverse=True)
+        elif delta_elem:
+            out = torch.empty(idx.raw_size, dtype=torch.uint8, device=dev)
+            ops.delta_filter(d_comp[:idx.raw_size], out, idx.block_raw,
+                             delta_elem, inverse=True)
         if verify:
             _verify_crcs_device(out, idx, dev)
         return out
@@ -678,6 +833,9 @@ def decode_device(d_comp, idx: ShardIndex, device, verify: bool = True):
         ops.byte_shuffle(out[:idx.raw_size], final[:idx.raw_size],
                          idx.block_raw, shuffle_elem, inverse=True)
         out = final
+    if delta_elem:
+        ops.delta_filter(out[:idx.raw_size], out[:idx.raw_size],
+                         idx.block_raw, delta_elem, inverse=True)
     if verify:
         _verify_crcs_device(out, idx, dev)
     return out[:idx.raw_size]
@@ -708,9 +866,10 @@ def unpack_gpu(buf: bytes, device=None, verify: bool = True):
 
 
 def pack_file(src: Path, dst: Path, block_raw: int = DEFAULT_BLOCK_RAW,
-              compress: bool = True, shuffle_elem: int = 0) -> ShardIndex:
+              compress: bool = True, shuffle_elem: int = 0,
+              delta_elem: int = 0) -> ShardIndex:
     data = Path(src).read_bytes()
     packed = pack(data, block_raw=block_raw, compress=compress,
-                  shuffle_elem=shuffle_elem)
+                  shuffle_elem=shuffle_elem, delta_elem=delta_elem)
     Path(dst).write_bytes(packed)
     return read_index(packed)

@@ -134,8 +134,9 @@ class ShardStager:
                     f"{p}: truncated inside the SYSHARD header")
             _, flags, block_raw, raw_size, n_blocks = \
                 shardfmt.HEADER.unpack(head)
-            # ValueError for a FILTER_SHUFFLE flag with a bad element size
+            # ValueError for a filter flag with a bad element size
             shuffle_elem = shardfmt.shuffle_elem_from_flags(flags)
+            delta_elem = shardfmt.delta_elem_from_flags(flags)
             table_bytes = shardfmt.ENTRY.size * n_blocks
             if size - shardfmt.HEADER.size < table_bytes:
                 raise ValueError(
@@ -157,7 +158,7 @@ class ShardStager:
             block_raw=block_raw, raw_size=raw_size, payload_off=0,
             table=np.frombuffer(table, dtype=shardfmt._entry_dt(),
                                 count=n_blocks),
-            shuffle_elem=shuffle_elem)
+            shuffle_elem=shuffle_elem, delta_elem=delta_elem)
         # the upload buffer is at least 1 byte; hand the decoder the true
         # payload length so validate_index bounds the table against it
         out = self._decode(d_payload[:payload_total], idx)

@@ -41,9 +41,12 @@ class ObjectStore:
     def upload_bytes(self, remote_path: str, data: bytes,
                      pack: bool = False,
                      manifest: bool = False,
-                     shuffle_elem: int = 0) -> Path:
+                     shuffle_elem: int = 0,
+                     delta_elem: int = 0) -> Path:
         """``shuffle_elem`` (with ``pack``): byte-shuffle filter element
-        size for typed numeric payloads, see shardfmt.pack."""
+        size for typed numeric payloads; ``delta_elem``: delta filter
+        element size for monotone ones (offsets, sorted ids,
+        timestamps).  See shardfmt.pack."""
         dst = self._path(remote_path)
         dst.parent.mkdir(parents=True, exist_ok=True)
         if pack:
@@ -52,7 +55,8 @@ class ObjectStore:
             # threaded CPU matcher otherwise
             workers = 0 if len(data) > (4 << 20) else None
             dst.write_bytes(shardfmt.pack_auto(
-                data, workers=workers, shuffle_elem=shuffle_elem))
+                data, workers=workers, shuffle_elem=shuffle_elem,
+                delta_elem=delta_elem))
         else:
             dst.write_bytes(data)
         if manifest:
@@ -61,12 +65,14 @@ class ObjectStore:
 
     def upload_file(self, local_path, remote_path: str,
                     pack: bool = False, manifest: bool = False,
-                    shuffle_elem: int = 0) -> Path:
+                    shuffle_elem: int = 0,
+                    delta_elem: int = 0) -> Path:
         data = Path(local_path).read_bytes() if (pack or manifest) else None
         if pack or manifest:
             return self.upload_bytes(remote_path, data, pack=pack,
                                      manifest=manifest,
-                                     shuffle_elem=shuffle_elem)
+                                     shuffle_elem=shuffle_elem,
+                                     delta_elem=delta_elem)
         dst = self._path(remote_path)
         dst.parent.mkdir(parents=True, exist_ok=True)
         shutil.copy2(local_path, dst)

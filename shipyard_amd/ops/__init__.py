@@ -125,6 +125,8 @@ def _load() -> ctypes.CDLL:
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32,
         ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p,
     ]
+    lib.sy_delta_filter.restype = ctypes.c_int
+    lib.sy_delta_filter.argtypes = lib.sy_byte_shuffle.argtypes
     lib.sy_lz4_compress_blocks_gpu.restype = ctypes.c_int
     lib.sy_lz4_compress_blocks_gpu.argtypes = [
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
@@ -457,6 +459,73 @@ def byte_shuffle(src, dst, block_raw: int, elem_size: int,
         ctypes.c_uint32(elem_size), ctypes.c_int(int(bool(inverse))),
         _stream())
     _check(rc, "sy_byte_shuffle")
+
+
+DELTA_ELEM_SIZES = (2, 4, 8)
+DELTA_BLOCK_ALIGN = 4096
+
+
+def delta_filter(src, dst, block_raw: int, elem_size: int,
+                 inverse: bool = False):
+    """SYSHARD delta filter on the device: ``dst`` receives ``src`` with
+    every ``block_raw`` block (the last one may be short) turned into
+    differences of its ``elem_size``-byte little-endian unsigned
+    elements mod 2**(8*elem_size) — ``d[0] = x[0]``,
+    ``d[i] = x[i] - x[i-1]``, restarting at every block, the
+    ``len % elem_size`` leftover copied verbatim.  ``inverse=True`` sums
+    them up again (one inclusive scan per block).  The byte layout is
+    ``shardfmt.delta_blocks_numpy``'s.
+
+    ``src``/``dst``: contiguous uint8 CUDA tensors of equal numel whose
+    base pointers are 16-byte aligned.  ``dst`` may be ``src`` itself
+    (same base, same length: the filter then runs in place, in either
+    direction); any other overlap of the byte ranges is a ValueError.
+    ``elem_size`` in {2, 4, 8}; ``block_raw`` a positive multiple of 4096
+    below 2**32.  Each violation is a ValueError raised before any
+    launch (and ahead of the device assert, so the rules are testable
+    on hosts without a GPU).
+
+    One workgroup decodes one block from start to end, so a buffer of a
+    few very large blocks uses only a few CUs."""
+    import torch
+
+    for t, name in ((src, "src"), (dst, "dst")):
+        assert t.dtype == torch.uint8 and t.is_contiguous(), \
+            f"delta_filter: {name}"
+        if t.data_ptr() % 16:
+            raise ValueError(
+                f"delta_filter: {name} base pointer must be 16-byte "
+                f"aligned (tensor storage offset {t.storage_offset()}); "
+                "pass an aligned view or .clone() it")
+    n = src.numel()
+    if dst.numel() != n:
+        raise ValueError(
+            f"delta_filter: src has {n} bytes but dst {dst.numel()}")
+    if n and src.data_ptr() != dst.data_ptr() and \
+            src.data_ptr() < dst.data_ptr() + n and \
+            dst.data_ptr() < src.data_ptr() + n:
+        raise ValueError(
+            "delta_filter: src and dst overlap partially (in place "
+            "means the same base and length)")
+    if elem_size not in DELTA_ELEM_SIZES:
+        raise ValueError(
+            f"delta_filter: elem_size={elem_size} not in "
+            f"{DELTA_ELEM_SIZES}")
+    if not 0 < block_raw < (1 << 32) or block_raw % DELTA_BLOCK_ALIGN:
+        raise ValueError(
+            f"delta_filter: block_raw={block_raw} must be a positive "
+            f"multiple of {DELTA_BLOCK_ALIGN} below 2**32")
+    assert src.is_cuda and dst.is_cuda and src.device == dst.device, \
+        "delta_filter: CUDA tensors on one device"
+    if n == 0:
+        return
+    lib = _load()
+    rc = lib.sy_delta_filter(
+        ctypes.c_void_p(src.data_ptr()), ctypes.c_void_p(dst.data_ptr()),
+        ctypes.c_uint64(n), ctypes.c_uint32(block_raw),
+        ctypes.c_uint32(elem_size), ctypes.c_int(int(bool(inverse))),
+        _stream())
+    _check(rc, "sy_delta_filter")
 
 
 def _env_atoi(name: str, default: int) -> int:

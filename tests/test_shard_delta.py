@@ -1,0 +1,398 @@
+"""SYSHARD FILTER_DELTA (delta filter for monotone typed shards) on the
+CPU: the reference semantics spelled out by hand, header rules, CPU
+writer/reader round trips, the ops.delta_filter argument guards (they
+fire before the device assert) and the decode_device orchestration
+against strict stub ops.  The device kernel itself is covered by
+tests/test_delta_gpu (-m gpu)."""
+import os
+import struct
+import sys
+
+import numpy as np
+import pytest
+
+torch = pytest.importorskip("torch")
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from shard_delta_stub_ops import (FilterOps, decode_index,  # noqa: E402
+                                  decode_packed)
+
+from shipyard_amd import ops  # noqa: E402
+from shipyard_amd.data import shardfmt  # noqa: E402
+from shipyard_amd.data.storage import ObjectStore  # noqa: E402
+from shipyard_amd.ops import gf2  # noqa: E402
+
+ELEMS = (2, 4, 8)
+BLOCKS = (4096, 8192)
+
+
+def _lengths(E):
+    return sorted({0, 1, E - 1, E, E + 1, 4095, 4096, 4097, 3 * 8192 + 5})
+
+
+def _rand(n, seed):
+    return np.random.default_rng(seed).integers(
+        0, 256, n, dtype=np.uint8).tobytes()
+
+
+def _offsets(n_el, seed, dtype="<i8"):
+    """Monotone content: cumulative Poisson(40) steps."""
+    rng = np.random.default_rng(seed)
+    return np.cumsum(rng.poisson(40, n_el)).astype(dtype).tobytes()
+
+
+def _header_flags(packed):
+    return struct.unpack_from("<I", packed, 8)[0]
+
+
+def _le(vals, E):
+    return b"".join(int(v).to_bytes(E, "little") for v in vals)
+
+
+# ------------------------------------------------------------- semantics
+@pytest.mark.parametrize("E", ELEMS)
+def test_reference_semantics_by_hand(E):
+    M = 1 << (8 * E)
+    # block 0: four elements, wraparound below 0 and at M - 1;
+    # block 1 (ragged): the running value restarts, then E - 1 leftover
+    # bytes that are not an element
+    blk0 = [3, 0, M - 1, 1]
+    blk1 = [7, 7]
+    left = b"\xee" * (E - 1)
+    raw = _le(blk0, E) + _le(blk1, E) + left
+    want = (_le([3, M - 3, M - 1, 2], E)   # 0-3, (M-1)-0, 1-(M-1) mod M
+            + _le([7, 0], E)               # d[0] = x[0] again, not 7 - 1
+            + left)
+    got = shardfmt.delta_blocks_numpy(raw, 4 * E, E)
+    assert got == want
+    assert shardfmt.delta_blocks_numpy(got, 4 * E, E, inverse=True) == raw
+    # the same bytes as ONE block: the second run continues the first
+    one = shardfmt.delta_blocks_numpy(raw, 4096, E)
+    assert one[4 * E:5 * E] == _le([(7 - 1) % M], E)
+    assert one[6 * E:] == left
+
+
+@pytest.mark.parametrize("B", BLOCKS)
+@pytest.mark.parametrize("E", ELEMS)
+def test_reference_inverse_is_identity(E, B):
+    for n in _lengths(E):
+        x = _rand(n, seed=7 * n + E)
+        f = shardfmt.delta_blocks_numpy(x, B, E)
+        assert len(f) == n
+        assert shardfmt.delta_blocks_numpy(f, B, E, inverse=True) == x
+        # the definition, element by element, on every block
+        M = 1 << (8 * E)
+        for lo in range(0, n, B):
+            raw, flt = x[lo:lo + B], f[lo:lo + B]
+            body = len(raw) // E * E
+            for i in range(0, body, 97 * E):  # sampled
+                cur = int.from_bytes(raw[i:i + E], "little")
+                prev = int.from_bytes(raw[i - E:i], "little") if i else 0
+                assert int.from_bytes(flt[i:i + E], "little") == \
+                    (cur - prev) % M
+            assert flt[body:] == raw[body:]
+            assert flt[:E] == raw[:E]  # the running value restarted
+
+
+def test_reference_rejects_bad_arguments():
+    for E in (0, 1, 3, 16):
+        with pytest.raises(ValueError, match="elem_size"):
+            shardfmt.delta_blocks_numpy(b"abcd", 4096, E)
+    with pytest.raises(ValueError, match="block_raw"):
+        shardfmt.delta_blocks_numpy(b"abcd", 0, 4)
+
+
+# ---------------------------------------------------------------- header
+def test_header_bits():
+    x = _offsets(2048, seed=1)
+    packed = shardfmt.pack(x, delta_elem=8)
+    assert _header_flags(packed) == 0x4 | (8 << 16) | 0x1
+    idx = shardfmt.read_index(packed)
+    assert idx.delta_elem == 8 and idx.shuffle_elem == 0
+    packed = shardfmt.pack(x, delta_elem=8, shuffle_elem=4)
+    assert _header_flags(packed) == 0x4 | (8 << 16) | 0x2 | (4 << 8) | 0x1
+    idx = shardfmt.read_index(packed)
+    assert idx.delta_elem == 8 and idx.shuffle_elem == 4
+    packed = shardfmt.pack(x, delta_elem=2, compress=False)
+    assert _header_flags(packed) == 0x4 | (2 << 16)
+
+
+def test_format_pin():
+    raw = _le([10, 13, 13, 12], 4) + b"xyz"
+    packed = shardfmt.pack(raw, block_raw=4096, compress=False,
+                           delta_elem=4)
+    assert _header_flags(packed) == 0x40004
+    idx = shardfmt.read_index(packed)
+    want = _le([10, 3, 0, 0xFFFFFFFF], 4) + b"xyz"
+    assert packed[idx.payload_off:idx.payload_off + 19] == want
+    assert int(idx.table["crc"][0]) == gf2.crc32c(raw)
+    assert shardfmt.unpack_cpu(packed) == raw
+    # delta first, then shuffle
+    both = shardfmt.pack(raw, block_raw=4096, compress=False,
+                         delta_elem=4, shuffle_elem=4)
+    idx = shardfmt.read_index(both)
+    assert both[idx.payload_off:idx.payload_off + 19] == \
+        shardfmt.shuffle_blocks_numpy(want, 4096, 4)
+    assert shardfmt.unpack_cpu(both) == raw
+
+
+@pytest.mark.parametrize("D", [0, 1, 3, 16])
+def test_read_index_rejects_bad_elem(D):
+    hdr = shardfmt.HEADER.pack(shardfmt.MAGIC, 0x5 | (D << 16), 4096, 0, 0)
+    with pytest.raises(ValueError, match="FILTER_DELTA"):
+        shardfmt.read_index(hdr)
+
+
+def test_elem_bits_ignored_without_the_flag():
+    for D in (0, 1, 3, 8, 16, 255):
+        hdr = shardfmt.HEADER.pack(shardfmt.MAGIC, 0x1 | (D << 16), 4096,
+                                   0, 0)
+        idx = shardfmt.read_index(hdr)
+        assert idx.delta_elem == 0 and idx.shuffle_elem == 0
+    # positional construction as before the keyword existed
+    assert shardfmt.ShardIndex(4096, 0, 0).delta_elem == 0
+
+
+def test_validate_index_enforces_elem():
+    for D in (1, 3, 16):
+        idx = shardfmt.ShardIndex(block_raw=4096, raw_size=0,
+                                  payload_off=0, delta_elem=D)
+        with pytest.raises(ValueError, match="delta_elem"):
+            shardfmt.validate_index(idx, 0)
+    for D in (0, 2, 4, 8):
+        shardfmt.validate_index(
+            shardfmt.ShardIndex(block_raw=4096, raw_size=0, payload_off=0,
+                                delta_elem=D, shuffle_elem=4), 0)
+
+
+def test_writers_reject_bad_elem(tmp_path):
+    for fn in (shardfmt.pack, shardfmt.pack_auto):
+        with pytest.raises(ValueError, match="delta_elem"):
+            fn(b"abcd" * 10, delta_elem=3)
+    # pack_gpu checks its arguments before it touches a device
+    with pytest.raises(ValueError, match="delta_elem"):
+        shardfmt.pack_gpu(b"abcd" * 10, delta_elem=3)
+    (tmp_path / "in.bin").write_bytes(b"abcd" * 10)
+    with pytest.raises(ValueError, match="delta_elem"):
+        shardfmt.pack_file(tmp_path / "in.bin", tmp_path / "o.syshard",
+                           delta_elem=3)
+    store = ObjectStore(tmp_path / "store")
+    with pytest.raises(ValueError, match="delta_elem"):
+        store.upload_bytes("a.bin", b"abcd" * 10, pack=True, delta_elem=3)
+
+
+# ----------------------------------------------------------- round trips
+@pytest.mark.parametrize("compress", [True, False])
+@pytest.mark.parametrize("S", [0, 2, 4, 8])
+@pytest.mark.parametrize("D", ELEMS)
+def test_round_trip(D, S, compress):
+    for n_el, tail in ((0, 0), (1, 0), (1025, 3), (3 * 1024 + 7, 5)):
+        x = _offsets(n_el, seed=n_el + D) + _rand(tail, seed=tail)
+        packed = shardfmt.pack(x, block_raw=4096, compress=compress,
+                               delta_elem=D, shuffle_elem=S)
+        want = 0x4 | (D << 16) | int(compress)
+        if S:
+            want |= 0x2 | (S << 8)
+        assert _header_flags(packed) == want
+        assert shardfmt.unpack_cpu(packed) == x, (D, S, n_el, compress)
+    x = _rand(2 * 8192 + 77, seed=D * 8 + S)  # every delta wraps
+    packed = shardfmt.pack(x, compress=compress, delta_elem=D,
+                           shuffle_elem=S)
+    assert shardfmt.unpack_cpu(packed) == x
+
+
+def test_delta_elem_zero_is_byte_identical():
+    x = _offsets(3 * 1024 + 1, seed=5) + os.urandom(9000)
+    for compress in (True, False):
+        for S in (0, 4):
+            plain = shardfmt.pack(x, compress=compress, shuffle_elem=S)
+            assert plain == shardfmt.pack(x, compress=compress,
+                                          shuffle_elem=S, delta_elem=0)
+            assert not _header_flags(plain) & 0x00FF0004
+            assert shardfmt.read_index(plain).delta_elem == 0
+            assert shardfmt.unpack_cpu(plain) == x
+    assert shardfmt.pack_auto(x) == shardfmt.pack_auto(x, delta_elem=0)
+
+
+def test_pack_file_forwards_the_filter(tmp_path):
+    x = _offsets(1024 + 3, seed=6)
+    (tmp_path / "in.bin").write_bytes(x)
+    idx = shardfmt.pack_file(tmp_path / "in.bin", tmp_path / "out.syshard",
+                             delta_elem=8, shuffle_elem=8)
+    assert idx.delta_elem == 8 and idx.shuffle_elem == 8
+    assert shardfmt.unpack_cpu((tmp_path / "out.syshard").read_bytes()) == x
+
+
+def test_reader_without_the_flag_fails_its_crc():
+    """Clearing bit 2 is what a reader that ignores the flag sees: it
+    must fail loudly, not return differences."""
+    x = _offsets(1024 + 13, seed=10)
+    for compress in (True, False):
+        packed = bytearray(shardfmt.pack(x, compress=compress,
+                                         delta_elem=8))
+        flags = _header_flags(packed)
+        struct.pack_into("<I", packed, 8, flags & ~0x4)
+        with pytest.raises(ValueError, match="CRC mismatch"):
+            shardfmt.unpack_cpu(bytes(packed))
+
+
+def test_crc_protects_filtered_shard():
+    x = _offsets(3 * 1024 + 9, seed=9)
+    for compress in (True, False):
+        packed = bytearray(shardfmt.pack(x, compress=compress,
+                                         delta_elem=8, shuffle_elem=8))
+        idx = shardfmt.read_index(bytes(packed))
+        packed[idx.payload_off + 8] ^= 0x55
+        with pytest.raises(ValueError, match="CRC mismatch"):
+            shardfmt.unpack_cpu(bytes(packed))
+
+
+def test_size_benefit_on_cumulative_offsets():
+    """CSR-style offsets, the case the filter exists for.  Python packer
+    and native CPU packer alike: plain 137372, shuffle 55756, delta +
+    shuffle 35340 of 262144 raw bytes (0.524 / 0.213 / 0.135)."""
+    x = np.cumsum(np.random.default_rng(1).poisson(40, 32768)).astype(
+        "<i8").tobytes()
+    plain = shardfmt.pack(x)
+    shuf = shardfmt.pack(x, shuffle_elem=8)
+    both = shardfmt.pack(x, delta_elem=8, shuffle_elem=8)
+    print(f"offset shard of {len(x)}: plain {len(plain)} shuffle "
+          f"{len(shuf)} delta+shuffle {len(both)}")
+    assert len(both) < len(shuf) < len(plain)
+    assert shardfmt.unpack_cpu(both) == x
+
+
+# ------------------------------------------------- binding argument rules
+def test_delta_filter_guards_fire_without_a_device():
+    buf = torch.zeros(2 * 8192 + 64, dtype=torch.uint8)
+    base = (-buf.data_ptr()) % 16
+    src = buf[base:base + 4096]
+    dst = buf[base + 8192:base + 8192 + 4096]
+    with pytest.raises(ValueError, match="16-byte aligned"):
+        ops.delta_filter(buf[base + 1:base + 1 + 4096], dst, 4096, 4)
+    with pytest.raises(ValueError, match="16-byte aligned"):
+        ops.delta_filter(src, buf[base + 8200:base + 8200 + 4096], 4096, 4)
+    with pytest.raises(ValueError, match="bytes but dst"):
+        ops.delta_filter(src, buf[base + 8192:base + 8192 + 4080], 4096, 4)
+    with pytest.raises(ValueError, match="overlap"):
+        ops.delta_filter(src, buf[base + 16:base + 16 + 4096], 4096, 4)
+    with pytest.raises(ValueError, match="overlap"):
+        ops.delta_filter(buf[base + 4080:base + 4080 + 4096], src, 4096, 4,
+                         inverse=True)
+    for E in (0, 1, 3, 16):
+        with pytest.raises(ValueError, match="elem_size"):
+            ops.delta_filter(src, dst, 4096, E)
+        with pytest.raises(ValueError, match="elem_size"):
+            ops.delta_filter(src, src, 4096, E)  # in place: same rules
+    for B in (0, -4096, 100, 4097, 6144, 1 << 32):
+        with pytest.raises(ValueError, match="block_raw"):
+            ops.delta_filter(src, dst, B, 4)
+    assert not buf.any()  # nothing ran
+
+
+# ------------------------------------------- decode_device through stubs
+def _mixed(n_tail=1001):
+    """Compressible offsets, an incompressible stretch (stored blocks)
+    and a ragged final block."""
+    return (_offsets(2 * 1024, seed=3) + os.urandom(8192)
+            + _offsets(1024, seed=4) + _rand(n_tail, seed=5))
+
+
+@pytest.mark.parametrize("S", [0, 8, 2], ids=["delta", "delta+shuf8",
+                                              "delta+shuf2"])
+@pytest.mark.parametrize("path", ["compressed", "mixed", "stored"])
+def test_decode_device_orchestration(path, S):
+    """Host side of the GPU reader: un-delta is the last kernel before
+    the CRC, runs in place except when it reads the payload itself, and
+    never touches the payload."""
+    if path == "compressed":
+        x, compress = _offsets(3 * 1024 + 100, seed=8), True
+    elif path == "mixed":
+        x, compress = _mixed(), True
+    else:
+        x, compress = _mixed(), False
+    packed = shardfmt.pack(x, block_raw=8192, compress=compress,
+                           delta_elem=8, shuffle_elem=S)
+    idx = shardfmt.read_index(packed)
+    stored = idx.table["comp_len"] == idx.table["raw_len"]
+    if path == "compressed":
+        assert not stored.any()
+    elif path == "mixed":
+        assert stored.any() and not stored.all()
+    else:
+        assert shardfmt._stored_contiguous(idx)
+    payload = packed[idx.payload_off:]
+    fake = FilterOps()
+    out, d_comp = decode_packed(packed, fake)
+    assert bytes(out.numpy().tobytes()) == x
+    assert bytes(d_comp.numpy().tobytes()) == payload  # payload unchanged
+    lo, hi = d_comp.data_ptr(), d_comp.data_ptr() + d_comp.numel()
+    assert not lo <= out.data_ptr() < hi                # and not aliased
+
+    kinds = [k for k, _ in fake.calls]
+    deltas = [k for k in kinds if k.startswith("delta")]
+    assert len(deltas) == 1 and kinds.count("shuffle") == (1 if S else 0)
+    assert kinds[-1] == "crc" and kinds[-2] == deltas[0]
+    if S:
+        assert kinds.index("shuffle") < kinds.index(deltas[0])
+    if path == "stored":
+        # no gather: delta alone reads the payload into a new tensor,
+        # with a shuffle the unshuffle does and un-delta is in place
+        want = ["shuffle", "delta-inplace", "crc"] if S else \
+            ["delta", "crc"]
+        assert kinds == want
+    else:
+        assert deltas == ["delta-inplace"]
+
+    bad = bytearray(packed)
+    bad[idx.payload_off + 3] ^= 0x40
+    with pytest.raises(ValueError):  # CRC, or the LZ4 stream itself
+        decode_packed(bytes(bad), FilterOps())
+
+
+def test_decode_device_corrupt_index_launches_nothing():
+    x = _mixed()
+    packed = shardfmt.pack(x, block_raw=8192, delta_elem=8, shuffle_elem=8)
+    idx = shardfmt.read_index(packed)
+    payload = packed[idx.payload_off:]
+
+    table = idx.table.copy()
+    table["comp_off"][1] += 8  # misaligned block start
+    fake = FilterOps()
+    with pytest.raises(ValueError, match="16-byte aligned"):
+        decode_index(shardfmt.ShardIndex(
+            idx.block_raw, idx.raw_size, 0, table=table, delta_elem=8,
+            shuffle_elem=8), payload, fake)
+    assert fake.launches == 0
+
+    table = idx.table.copy()
+    table["comp_len"][-1] = len(payload) + 1  # past the payload
+    with pytest.raises(ValueError):
+        decode_index(shardfmt.ShardIndex(
+            idx.block_raw, idx.raw_size, 0, table=table, delta_elem=8),
+            payload, fake)
+    assert fake.launches == 0
+
+    with pytest.raises(ValueError, match="delta_elem"):
+        decode_index(shardfmt.ShardIndex(
+            idx.block_raw, idx.raw_size, 0, table=idx.table, delta_elem=3),
+            payload, fake)
+    assert fake.launches == 0
+
+
+# ------------------------------------------------------------ object store
+def test_object_store_round_trip(tmp_path):
+    store = ObjectStore(tmp_path / "store")
+    x = _offsets(5000, seed=2) + b"\x01\x02\x03"
+    p = store.upload_bytes("offsets/a.bin", x, pack=True, delta_elem=8,
+                           shuffle_elem=8)
+    idx = shardfmt.read_index(p.read_bytes())
+    assert idx.delta_elem == 8 and idx.shuffle_elem == 8
+    assert store.download_bytes("offsets/a.bin") == x
+    src = tmp_path / "local.bin"
+    src.write_bytes(x)
+    p2 = store.upload_file(src, "offsets/b.bin", pack=True, delta_elem=4)
+    idx = shardfmt.read_index(p2.read_bytes())
+    assert idx.delta_elem == 4 and idx.shuffle_elem == 0
+    assert store.download_bytes("offsets/b.bin") == x
