@@ -57,14 +57,23 @@ crc32c is again that of the ORIGINAL bytes.  The filter is opt-in per
 shard: data that is not monotone (uniform token ids) gets WORSE under
 delta, because differences of independent values are noisier than the
 values.
+
+Adding a filter: add a row to ``FILTERS`` at its place in the writer
+order (flag bit, element-size bits, whether the device op may run in
+place), a numpy body transform for ``_filter_blocks`` as its reference,
+an ``ops`` binding with the arguments of ``ops.byte_shuffle``, and the
+kernel behind it; then add the row's keyword to the writers' signatures
+and to ``ShardIndex``.  Flags, header parsing, validation and the CPU
+and device chains in both directions all follow from the row.
 """
 from __future__ import annotations
 
 import io
 import struct
+from collections import namedtuple
 from dataclasses import dataclass
 from pathlib import Path
-from typing import List, Optional
+from typing import Callable, List, Optional
 
 from shipyard_amd.data import lz4py
 from shipyard_amd.ops import gf2
@@ -85,72 +94,55 @@ DEFAULT_BLOCK_RAW = 8 * 1024
 GPU_BLOCK_ALIGN = 4096
 GPU_LZ4_BLOCK_MAX = 64 * 1024
 FLAG_LZ4 = 0x1
-FLAG_FILTER_SHUFFLE = 0x2
-SHUFFLE_ELEM_SHIFT = 8
-SHUFFLE_ELEM_SIZES = (2, 4, 8)
-FLAG_FILTER_DELTA = 0x4
-DELTA_ELEM_SHIFT = 16
-DELTA_ELEM_SIZES = (2, 4, 8)
+FILTER_ELEM_SIZES = (2, 4, 8)
 
 
-def _check_shuffle_elem(shuffle_elem: int, what: str) -> int:
-    if shuffle_elem != 0 and shuffle_elem not in SHUFFLE_ELEM_SIZES:
-        raise ValueError(
-            f"{what}: shuffle_elem={shuffle_elem} must be 0 (no filter) "
-            f"or one of {SHUFFLE_ELEM_SIZES}")
-    return int(shuffle_elem)
+def _filter_blocks(data, block_raw: int, elem_size: int, inverse: bool,
+                   body_fn) -> bytes:
+    """Walk ``data`` as ``block_raw`` blocks (the last may be short):
+    ``body_fn(x, elem_size, inverse)`` transforms the whole elements of
+    a batch of equally long blocks, an ``(n_blk, body)`` uint8 view,
+    and the ``len % elem_size`` leftover of every block is copied
+    verbatim.  One call for all full blocks, one for the ragged one."""
+    import numpy as np
+
+    if elem_size not in FILTER_ELEM_SIZES:
+        raise ValueError(f"elem_size={elem_size} not in {FILTER_ELEM_SIZES}")
+    if block_raw <= 0:
+        raise ValueError("block_raw must be positive")
+    src = np.frombuffer(data, dtype=np.uint8)
+    out = np.empty_like(src)
+    n_full, tail_len = divmod(len(src), block_raw)
+    for lo, n_blk, blk_len in ((0, n_full, block_raw),
+                               (n_full * block_raw, 1, tail_len)):
+        if not n_blk or not blk_len:
+            continue
+        body = blk_len // elem_size * elem_size
+        s = src[lo:lo + n_blk * blk_len].reshape(n_blk, blk_len)
+        d = out[lo:lo + n_blk * blk_len].reshape(n_blk, blk_len)
+        if body:
+            d[:, :body] = body_fn(s[:, :body], elem_size, inverse)
+        d[:, body:] = s[:, body:]
+    return out.tobytes()
 
 
-def shuffle_flags(shuffle_elem: int) -> int:
-    """The flags bits a writer sets for ``shuffle_elem`` (0 -> none)."""
-    if not shuffle_elem:
-        return 0
-    return FLAG_FILTER_SHUFFLE | (shuffle_elem << SHUFFLE_ELEM_SHIFT)
+def _shuffle_body(x, E: int, inverse: bool):
+    n_blk, body = x.shape
+    shape = (n_blk, E, body // E) if inverse else (n_blk, body // E, E)
+    return x.reshape(shape).transpose(0, 2, 1).reshape(n_blk, body)
 
 
-def shuffle_elem_from_flags(flags: int) -> int:
-    """Element size of the shuffle filter named by a header's flags
-    word; 0 when FILTER_SHUFFLE is clear (the element-size bits are
-    then ignored like every other unknown bit).  ValueError when the
-    filter is on with an element size other than 2, 4 or 8."""
-    if not flags & FLAG_FILTER_SHUFFLE:
-        return 0
-    elem = (flags >> SHUFFLE_ELEM_SHIFT) & 0xFF
-    if elem not in SHUFFLE_ELEM_SIZES:
-        raise ValueError(
-            f"SYSHARD flags {flags:#x}: FILTER_SHUFFLE with element "
-            f"size {elem}, must be one of {SHUFFLE_ELEM_SIZES}")
-    return elem
+def _delta_body(x, E: int, inverse: bool):
+    import numpy as np
 
-
-def _check_delta_elem(delta_elem: int, what: str) -> int:
-    if delta_elem != 0 and delta_elem not in DELTA_ELEM_SIZES:
-        raise ValueError(
-            f"{what}: delta_elem={delta_elem} must be 0 (no filter) "
-            f"or one of {DELTA_ELEM_SIZES}")
-    return int(delta_elem)
-
-
-def delta_flags(delta_elem: int) -> int:
-    """The flags bits a writer sets for ``delta_elem`` (0 -> none)."""
-    if not delta_elem:
-        return 0
-    return FLAG_FILTER_DELTA | (delta_elem << DELTA_ELEM_SHIFT)
-
-
-def delta_elem_from_flags(flags: int) -> int:
-    """Element size of the delta filter named by a header's flags word;
-    0 when FILTER_DELTA is clear (bits 16..23 are then ignored like
-    every other unknown bit).  ValueError when the filter is on with an
-    element size other than 2, 4 or 8."""
-    if not flags & FLAG_FILTER_DELTA:
-        return 0
-    elem = (flags >> DELTA_ELEM_SHIFT) & 0xFF
-    if elem not in DELTA_ELEM_SIZES:
-        raise ValueError(
-            f"SYSHARD flags {flags:#x}: FILTER_DELTA with element "
-            f"size {elem}, must be one of {DELTA_ELEM_SIZES}")
-    return elem
+    dt = np.dtype(f"<u{E}")
+    x = np.ascontiguousarray(x).view(dt)
+    if inverse:
+        y = np.cumsum(x, axis=1, dtype=dt)
+    else:
+        y = x.copy()
+        y[:, 1:] -= x[:, :-1]
+    return y.view(np.uint8)
 
 
 def shuffle_blocks_numpy(data, block_raw: int, elem_size: int,
@@ -162,33 +154,7 @@ def shuffle_blocks_numpy(data, block_raw: int, elem_size: int,
     one transpose for all full blocks, one for the ragged block.  The
     CPU writer, the CPU reader and the tests of the device kernel
     (ops.byte_shuffle) share it."""
-    import numpy as np
-
-    if elem_size not in SHUFFLE_ELEM_SIZES:
-        raise ValueError(f"elem_size={elem_size} not in {SHUFFLE_ELEM_SIZES}")
-    if block_raw <= 0:
-        raise ValueError("block_raw must be positive")
-    src = np.frombuffer(data, dtype=np.uint8)
-    out = np.empty_like(src)
-    n = len(src)
-    E = elem_size
-
-    def one(lo: int, n_blk: int, blk_len: int) -> None:
-        n_el = blk_len // E
-        body = n_el * E
-        s = src[lo:lo + n_blk * blk_len].reshape(n_blk, blk_len)
-        d = out[lo:lo + n_blk * blk_len].reshape(n_blk, blk_len)
-        shape = (n_blk, E, n_el) if inverse else (n_blk, n_el, E)
-        d[:, :body] = s[:, :body].reshape(shape).transpose(
-            0, 2, 1).reshape(n_blk, body)
-        d[:, body:] = s[:, body:]
-
-    n_full = n // block_raw
-    if n_full:
-        one(0, n_full, block_raw)
-    if n - n_full * block_raw:
-        one(n_full * block_raw, 1, n - n_full * block_raw)
-    return out.tobytes()
+    return _filter_blocks(data, block_raw, elem_size, inverse, _shuffle_body)
 
 
 def delta_blocks_numpy(data, block_raw: int, elem_size: int,
@@ -202,39 +168,118 @@ def delta_blocks_numpy(data, block_raw: int, elem_size: int,
     ``np.cumsum`` in the unsigned dtype) for all full blocks, one for
     the ragged block.  The CPU writer, the CPU reader and the tests of
     the device kernel (ops.delta_filter) share it."""
-    import numpy as np
+    return _filter_blocks(data, block_raw, elem_size, inverse, _delta_body)
 
-    if elem_size not in DELTA_ELEM_SIZES:
-        raise ValueError(f"elem_size={elem_size} not in {DELTA_ELEM_SIZES}")
-    if block_raw <= 0:
-        raise ValueError("block_raw must be positive")
-    src = np.frombuffer(data, dtype=np.uint8)
-    out = np.empty_like(src)
-    n = len(src)
-    E = elem_size
-    dt = np.dtype(f"<u{E}")
 
-    def one(lo: int, n_blk: int, blk_len: int) -> None:
-        n_el = blk_len // E
-        body = n_el * E
-        s = src[lo:lo + n_blk * blk_len].reshape(n_blk, blk_len)
-        d = out[lo:lo + n_blk * blk_len].reshape(n_blk, blk_len)
-        if n_el:
-            x = np.ascontiguousarray(s[:, :body]).view(dt)
-            if inverse:
-                y = np.cumsum(x, axis=1, dtype=dt)
-            else:
-                y = x.copy()
-                y[:, 1:] -= x[:, :-1]
-            d[:, :body] = y.view(np.uint8)
-        d[:, body:] = s[:, body:]
+@dataclass(frozen=True)
+class Filter:
+    """One row of FILTERS: everything the format code knows about a
+    block filter."""
+    kwarg: str         # keyword / ShardIndex attribute with its element size
+    flag_name: str     # the header flag, for messages
+    flag: int          # flags bit that turns the filter on
+    shift: int         # flags bits shift..shift+7 hold the element size
+    sizes: tuple       # element sizes the filter takes
+    numpy_fn: Callable  # reference: (data, block_raw, elem, inverse) -> bytes
+    op: str            # shipyard_amd.ops function with the same arguments
+    in_place: bool     # the op may run with dst == src
 
-    n_full = n // block_raw
-    if n_full:
-        one(0, n_full, block_raw)
-    if n - n_full * block_raw:
-        one(n_full * block_raw, 1, n - n_full * block_raw)
-    return out.tobytes()
+
+# in writer order; readers undo them in reverse
+FILTERS = (
+    Filter("delta_elem", "FILTER_DELTA", 0x4, 16, FILTER_ELEM_SIZES,
+           delta_blocks_numpy, "delta_filter", in_place=True),
+    Filter("shuffle_elem", "FILTER_SHUFFLE", 0x2, 8, FILTER_ELEM_SIZES,
+           shuffle_blocks_numpy, "byte_shuffle", in_place=False),
+)
+
+
+def _filter_elems(what: str, given) -> dict:
+    """``{keyword: element size}`` of every filter (0: off), in writer
+    order, from a mapping that holds them under their keyword names (a
+    writer's ``locals()``, a ShardIndex's ``vars()``).  ValueError in
+    ``what``'s name for a size the filter does not take."""
+    elems = {}
+    for f in FILTERS:
+        elem = given.get(f.kwarg, 0)
+        if elem != 0 and elem not in f.sizes:
+            raise ValueError(
+                f"{what}: {f.kwarg}={elem} must be 0 (no filter) "
+                f"or one of {f.sizes}")
+        elems[f.kwarg] = int(elem)
+    return elems
+
+
+def _active(elems: dict) -> list:
+    """(filter, element size) of the filters that are on, writer order."""
+    return [(f, elems[f.kwarg]) for f in FILTERS if elems[f.kwarg]]
+
+
+def filter_flags(elems: dict) -> int:
+    """The flags bits a writer sets for these element sizes."""
+    flags = 0
+    for f, elem in _active(elems):
+        flags |= f.flag | (elem << f.shift)
+    return flags
+
+
+def filter_elems_from_flags(flags: int) -> dict:
+    """Element size of every filter named by a header's flags word; 0
+    where the filter's bit is clear (its element-size bits are then
+    ignored like every other unknown bit).  ValueError when a filter is
+    on with an element size it does not take."""
+    elems = {}
+    for f in FILTERS:
+        elem = (flags >> f.shift) & 0xFF if flags & f.flag else 0
+        if flags & f.flag and elem not in f.sizes:
+            raise ValueError(
+                f"SYSHARD flags {flags:#x}: {f.flag_name} with element "
+                f"size {elem}, must be one of {f.sizes}")
+        elems[f.kwarg] = elem
+    return elems
+
+
+def filter_chain_numpy(data, block_raw: int, elems: dict,
+                       inverse: bool = False):
+    """Apply every active filter to ``data`` on the CPU in writer order,
+    or undo them in the reverse order with ``inverse``."""
+    steps = _active(elems)
+    for f, elem in (reversed(steps) if inverse else steps):
+        data = f.numpy_fn(data, block_raw, elem, inverse)
+    return data
+
+
+def filter_chain_device(t, block_raw: int, elems: dict):
+    """Writer side on the device: every active filter in order, each
+    into a freshly allocated tensor; rebinding ``t`` drops the
+    intermediate before it.  The tensor passed in is never written."""
+    import torch
+
+    from shipyard_amd import ops
+
+    for f, elem in _active(elems):
+        dst = torch.empty_like(t)
+        getattr(ops, f.op)(t, dst, block_raw, elem)
+        t = dst
+    return t
+
+
+def unfilter_chain_device(src, block_raw: int, elems: dict, borrowed: bool):
+    """Reader side on the device: undo the active filters in reverse
+    order and return the tensor that holds the result.  ``borrowed``
+    says that ``src`` is (a view of) the caller's payload, which is
+    never written (with no filter on, ``src`` itself comes back).  A
+    step gets a newly allocated destination when its source is borrowed
+    or its filter cannot run in place; otherwise it runs in place."""
+    import torch
+
+    from shipyard_amd import ops
+
+    for f, elem in reversed(_active(elems)):
+        dst = src if f.in_place and not borrowed else torch.empty_like(src)
+        getattr(ops, f.op)(src, dst, block_raw, elem, inverse=True)
+        src, borrowed = dst, False
+    return src
 
 
 @dataclass
@@ -348,15 +393,12 @@ def pack(data: bytes, block_raw: int = DEFAULT_BLOCK_RAW,
     independent LZ4 streams); None = serial, 0 = one per CPU.  The
     replicator/mover pass workers=0 so layer packing scales with cores
     (the pure-python compressor does ~12 MB/s per core)."""
-    _check_shuffle_elem(shuffle_elem, "pack")
-    _check_delta_elem(delta_elem, "pack")
+    elems = _filter_elems("pack", locals())
     crcs = gf2.crc32c_chunks_numpy(data, block_raw)
     n_raw = len(data)
-    if delta_elem and data:
-        data = delta_blocks_numpy(data, block_raw, delta_elem)
-    if shuffle_elem and data:
+    if data:
         # from here on `data` is what the payload holds: filtered bytes
-        data = shuffle_blocks_numpy(data, block_raw, shuffle_elem)
+        data = filter_chain_numpy(data, block_raw, elems)
     comps: List[bytes] = []
     if compress and data:
         # native multi-threaded compressor when the ops library is
@@ -405,8 +447,7 @@ def pack(data: bytes, block_raw: int = DEFAULT_BLOCK_RAW,
         pad = _align16(len(comp)) - len(comp)
         payload.write(b"\x00" * pad)
         off += len(comp) + pad
-    flags = (FLAG_LZ4 if compress else 0) | shuffle_flags(shuffle_elem) \
-        | delta_flags(delta_elem)
+    flags = (FLAG_LZ4 if compress else 0) | filter_flags(elems)
     hdr = HEADER.pack(MAGIC, flags, block_raw, n_raw, len(blocks))
     table = b"".join(ENTRY.pack(b.comp_off, b.comp_len, b.raw_len, b.crc32c)
                      for b in blocks)
@@ -448,9 +489,8 @@ def pack_gpu(data, block_raw: int = DEFAULT_BLOCK_RAW,
         raise ValueError(
             f"pack_gpu: block_raw={block_raw} must be a multiple of "
             f"{GPU_BLOCK_ALIGN} and at most {GPU_LZ4_BLOCK_MAX}")
-    _check_shuffle_elem(shuffle_elem, "pack_gpu")
-    _check_delta_elem(delta_elem, "pack_gpu")
-    flags = FLAG_LZ4 | shuffle_flags(shuffle_elem) | delta_flags(delta_elem)
+    elems = _filter_elems("pack_gpu", locals())
+    flags = FLAG_LZ4 | filter_flags(elems)
     import numpy as np
     import torch
 
@@ -477,17 +517,8 @@ def pack_gpu(data, block_raw: int = DEFAULT_BLOCK_RAW,
     # device-side CRC of every block (raw_cap chunks; ragged tail ok)
     crcs = np.asarray(ops.crc32c_chunks(t, chunk_size=block_raw)
                       .numpy(), dtype=np.uint32)
-    if delta_elem:
-        # the payload holds filtered bytes; the CRCs above do not
-        t_raw = t
-        t = torch.empty_like(t_raw)
-        ops.delta_filter(t_raw, t, block_raw, delta_elem)
-        del t_raw
-    if shuffle_elem:
-        t_raw = t
-        t = torch.empty_like(t_raw)
-        ops.byte_shuffle(t_raw, t, block_raw, shuffle_elem)
-        del t_raw
+    # the payload holds filtered bytes; the CRCs above do not
+    t = filter_chain_device(t, block_raw, elems)
     d_out, stride, lens = ops.lz4_compress_blocks_gpu(t, block_raw)
     lens_np = lens.numpy().view(np.uint32)
     n_blocks = (n + block_raw - 1) // block_raw
@@ -561,8 +592,7 @@ def pack_auto(data: bytes, block_raw: int = DEFAULT_BLOCK_RAW,
     handle (see ``pack_gpu``) always take the CPU writer.
     ``shuffle_elem`` and ``delta_elem`` go to whichever writer is
     picked."""
-    _check_shuffle_elem(shuffle_elem, "pack_auto")
-    _check_delta_elem(delta_elem, "pack_auto")
+    elems = _filter_elems("pack_auto", locals())
     if len(data) >= gpu_threshold and gpu_block_raw_ok(block_raw):
         try:
             import torch
@@ -571,31 +601,44 @@ def pack_auto(data: bytes, block_raw: int = DEFAULT_BLOCK_RAW,
         except Exception:
             use_gpu = False
         if use_gpu:
-            return pack_gpu(data, block_raw=block_raw,
-                            shuffle_elem=shuffle_elem,
-                            delta_elem=delta_elem)
-    return pack(data, block_raw=block_raw, workers=workers,
-                shuffle_elem=shuffle_elem, delta_elem=delta_elem)
+            return pack_gpu(data, block_raw=block_raw, **elems)
+    return pack(data, block_raw=block_raw, workers=workers, **elems)
 
 
-def read_index(buf: bytes) -> ShardIndex:
-    import numpy as np
+ShardHeader = namedtuple("ShardHeader", "block_raw raw_size n_blocks elems")
 
+
+def parse_header(buf) -> ShardHeader:
+    """The fixed header at the start of ``buf``; ``elems`` is the
+    {filter keyword: element size} of its flags.  ValueError for a short
+    buffer, a wrong magic or a filter flag with a bad element size."""
     if len(buf) < HEADER.size:
         raise ValueError("buffer shorter than the SYSHARD header")
     magic, flags, block_raw, raw_size, n_blocks = HEADER.unpack_from(buf, 0)
     if magic != MAGIC:
         raise ValueError("not a SYSHARD file")
-    shuffle_elem = shuffle_elem_from_flags(flags)
-    delta_elem = delta_elem_from_flags(flags)
-    if len(buf) - HEADER.size < n_blocks * ENTRY.size:
+    return ShardHeader(block_raw, raw_size, n_blocks,
+                       filter_elems_from_flags(flags))
+
+
+def index_from_table(hdr: ShardHeader, buf, offset: int = 0,
+                     payload_off: int = 0) -> ShardIndex:
+    """The index of a shard with header ``hdr`` whose block table starts
+    at ``buf[offset]`` (numpy view of ``buf``, no per-block python)."""
+    import numpy as np
+
+    if len(buf) - offset < hdr.n_blocks * ENTRY.size:
         raise ValueError("buffer shorter than the SYSHARD block table")
-    table = np.frombuffer(buf, dtype=_entry_dt(), count=n_blocks,
-                          offset=HEADER.size)
-    return ShardIndex(block_raw=block_raw, raw_size=raw_size,
-                      payload_off=HEADER.size + n_blocks * ENTRY.size,
-                      table=table, shuffle_elem=shuffle_elem,
-                      delta_elem=delta_elem)
+    table = np.frombuffer(buf, dtype=_entry_dt(), count=hdr.n_blocks,
+                          offset=offset)
+    return ShardIndex(block_raw=hdr.block_raw, raw_size=hdr.raw_size,
+                      payload_off=payload_off, table=table, **hdr.elems)
+
+
+def read_index(buf: bytes) -> ShardIndex:
+    hdr = parse_header(buf)
+    return index_from_table(hdr, buf, HEADER.size,
+                            HEADER.size + hdr.n_blocks * ENTRY.size)
 
 
 def validate_index(idx: ShardIndex, payload_len: int,
@@ -630,8 +673,7 @@ def validate_index(idx: ShardIndex, payload_len: int,
     payload_len = int(payload_len)
     if block_raw <= 0:
         raise ValueError("shard index: block_raw must be positive")
-    _check_shuffle_elem(getattr(idx, "shuffle_elem", 0), "shard index")
-    _check_delta_elem(getattr(idx, "delta_elem", 0), "shard index")
+    _filter_elems("shard index", vars(idx))
     want =(raw_size + block_raw - 1) // block_raw
     if n != want:
         raise ValueError(
@@ -679,18 +721,14 @@ def validate_index(idx: ShardIndex, payload_len: int,
 def unpack_cpu(buf: bytes, verify: bool = True) -> bytes:
     """CPU reference reader (tests + CPU-only hosts)."""
     idx = read_index(buf)
+    elems = _filter_elems("shard index", vars(idx))
     out = io.BytesIO()
     for b in idx.blocks:
         comp = buf[idx.payload_off + b.comp_off:
                    idx.payload_off + b.comp_off + b.comp_len]
         raw = comp if b.stored else lz4py.decompress_block(comp, b.raw_len)
-        if idx.shuffle_elem:
-            # one block per call: any block_raw >= raw_len keeps it whole
-            raw = shuffle_blocks_numpy(raw, max(len(raw), 1),
-                                       idx.shuffle_elem, inverse=True)
-        if idx.delta_elem:
-            raw = delta_blocks_numpy(raw, max(len(raw), 1),
-                                     idx.delta_elem, inverse=True)
+        # one block per call: any block_raw >= raw_len keeps it whole
+        raw = filter_chain_numpy(raw, max(len(raw), 1), elems, inverse=True)
         if verify and gf2.crc32c(raw) != b.crc32c:
             raise ValueError("CRC mismatch in shard block")
         out.write(raw)
@@ -741,70 +779,18 @@ def _verify_crcs_device(out, idx, dev) -> None:
         raise ValueError(f"GPU CRC mismatch in blocks {bad}")
 
 
-def decode_device(d_comp, idx: ShardIndex, device, verify: bool = True):
-    """Decode an uploaded shard payload in HBM: batched gather-copy for
-    stored blocks + wave-cooperative LZ4 for compressed ones + chunked
-    CRC verify.  All host work is vectorized (numpy column arrays) —
-    O(1) python regardless of block count.
-
-    The table is validated first (``validate_index`` against
-    ``d_comp.numel()``): a bad table raises ValueError before a tensor
-    is made or a kernel launched.
-
-    FILTER_SHUFFLE shards (``idx.shuffle_elem``) decode into a scratch
-    buffer, ops.byte_shuffle(inverse) writes the output from it, and the
-    CRCs are taken over the output — the unfiltered bytes the table's
-    CRCs describe.  Peak HBM use for such a shard is 2x raw (scratch +
-    output) on top of the payload; the stored-contiguous fast path
-    unshuffles straight from the payload into a new tensor instead of
-    aliasing it.  ``d_comp``'s base must then be 16-byte aligned.
-
-    FILTER_DELTA shards (``idx.delta_elem``) add one
-    ops.delta_filter(inverse) launch that runs IN PLACE on the output
-    tensor, after the unshuffle when both filters are on, and the CRCs
-    are taken after it.  So the peak stays what it was: 1x raw for
-    delta alone (the decode target is the output), 2x raw for delta +
-    shuffle.  On the stored-contiguous fast path with delta alone the
-    kernel reads the payload and writes a new tensor (1x raw), so the
-    payload is neither aliased nor modified; its base must be 16-byte
-    aligned there too."""
-    validate_index(idx, d_comp.numel(), for_gpu=True)
-
+def _decode_blocks(d_comp, idx: ShardIndex, dev):
+    """Gather the stored blocks and LZ4-decode the others into a new
+    raw_size tensor (still filtered when the shard has filters)."""
     import numpy as np
     import torch
 
     from shipyard_amd import ops
 
-    dev = device
-    shuffle_elem = idx.shuffle_elem
-    delta_elem = idx.delta_elem
-    if len(idx.table) == 0:
-        return torch.empty(0, dtype=torch.uint8, device=dev)
-    if _stored_contiguous(idx):
-        out = d_comp[:idx.raw_size]
-        if shuffle_elem:
-            out = torch.empty(idx.raw_size, dtype=torch.uint8, device=dev)
-            ops.byte_shuffle(d_comp[:idx.raw_size], out, idx.block_raw,
-                             shuffle_elem, inverse=True)
-            if delta_elem:
-                ops.delta_filter(out, out, idx.block_raw, delta_elem,
-                                 inverse=True)
-        elif delta_elem:
-            out = torch.empty(idx.raw_size, dtype=torch.uint8, device=dev)
-            ops.delta_filter(d_comp[:idx.raw_size], out, idx.block_raw,
-                             delta_elem, inverse=True)
-        if verify:
-            _verify_crcs_device(out, idx, dev)
-        return out
-
     t = idx.table
     raw_offs = idx.raw_offs()
     stored = t["comp_len"] == t["raw_len"]
-    out = torch.empty(max(idx.raw_size, 1), dtype=torch.uint8, device=dev)
-    if shuffle_elem:
-        # the kernels below fill `out`; keep that name on the scratch
-        # buffer and unshuffle into the real output afterwards
-        final = torch.empty_like(out)
+    out = torch.empty(idx.raw_size, dtype=torch.uint8, device=dev)
 
     def to_dev(arr, dtype):
         return torch.from_numpy(np.ascontiguousarray(arr)).to(dev).view(
@@ -829,16 +815,45 @@ def decode_device(d_comp, idx: ShardIndex, device, verify: bool = True):
         if not ops.lz4_all_ok(status):
             raise ValueError(
                 f"GPU LZ4 decode failed: status={status.cpu().tolist()}")
-    if shuffle_elem:
-        ops.byte_shuffle(out[:idx.raw_size], final[:idx.raw_size],
-                         idx.block_raw, shuffle_elem, inverse=True)
-        out = final
-    if delta_elem:
-        ops.delta_filter(out[:idx.raw_size], out[:idx.raw_size],
-                         idx.block_raw, delta_elem, inverse=True)
+    return out
+
+
+def decode_device(d_comp, idx: ShardIndex, device, verify: bool = True):
+    """Decode an uploaded shard payload in HBM: batched gather-copy for
+    stored blocks + wave-cooperative LZ4 for compressed ones + chunked
+    CRC verify.  All host work is vectorized (numpy column arrays) —
+    O(1) python regardless of block count.
+
+    The table is validated first (``validate_index`` against
+    ``d_comp.numel()``): a bad table raises ValueError before a tensor
+    is made or a kernel launched.
+
+    The shard's filters are undone by ``unfilter_chain_device`` and the
+    CRCs are taken after it, over the unfiltered bytes the table's CRCs
+    describe.  Its source is the decode target, or on the
+    stored-contiguous fast path the payload itself, which is never
+    aliased or modified: a filtered shard's output is then a new tensor
+    and ``d_comp``'s base must be 16-byte aligned.  Un-delta runs in
+    place on anything but the payload, unshuffle never does, so the
+    peak HBM use on top of the payload is 1x raw for delta alone and 2x
+    raw when shuffle is on."""
+    validate_index(idx, d_comp.numel(), for_gpu=True)
+
+    import torch
+
+    if len(idx.table) == 0:
+        return torch.empty(0, dtype=torch.uint8, device=device)
+    borrowed = _stored_contiguous(idx)
+    if borrowed:
+        src = d_comp[:idx.raw_size]
+    else:
+        src = _decode_blocks(d_comp, idx, device)
+    out = unfilter_chain_device(
+        src, idx.block_raw, _filter_elems("shard index", vars(idx)),
+        borrowed)
     if verify:
-        _verify_crcs_device(out, idx, dev)
-    return out[:idx.raw_size]
+        _verify_crcs_device(out, idx, device)
+    return out
 
 
 def unpack_gpu(buf: bytes, device=None, verify: bool = True):
@@ -870,6 +885,6 @@ def pack_file(src: Path, dst: Path, block_raw: int = DEFAULT_BLOCK_RAW,
               delta_elem: int = 0) -> ShardIndex:
     data = Path(src).read_bytes()
     packed = pack(data, block_raw=block_raw, compress=compress,
-                  shuffle_elem=shuffle_elem, delta_elem=delta_elem)
+                  **_filter_elems("pack_file", locals()))
     Path(dst).write_bytes(packed)
     return read_index(packed)

@@ -132,12 +132,9 @@ class ShardStager:
             if len(head) < shardfmt.HEADER.size:
                 raise ValueError(
                     f"{p}: truncated inside the SYSHARD header")
-            _, flags, block_raw, raw_size, n_blocks = \
-                shardfmt.HEADER.unpack(head)
             # ValueError for a filter flag with a bad element size
-            shuffle_elem = shardfmt.shuffle_elem_from_flags(flags)
-            delta_elem = shardfmt.delta_elem_from_flags(flags)
-            table_bytes = shardfmt.ENTRY.size * n_blocks
+            hdr = shardfmt.parse_header(head)
+            table_bytes = shardfmt.ENTRY.size * hdr.n_blocks
             if size - shardfmt.HEADER.size < table_bytes:
                 raise ValueError(
                     f"{p}: truncated inside the SYSHARD block table")
@@ -152,21 +149,15 @@ class ShardStager:
                 d_payload = self._upload(f, payload_total)
 
         # parse table on host (numpy, O(1) python), decode in HBM
-        import numpy as np
-
-        idx = shardfmt.ShardIndex(
-            block_raw=block_raw, raw_size=raw_size, payload_off=0,
-            table=np.frombuffer(table, dtype=shardfmt._entry_dt(),
-                                count=n_blocks),
-            shuffle_elem=shuffle_elem, delta_elem=delta_elem)
+        idx = shardfmt.index_from_table(hdr, table)
         # the upload buffer is at least 1 byte; hand the decoder the true
         # payload length so validate_index bounds the table against it
         out = self._decode(d_payload[:payload_total], idx)
         sec = time.perf_counter() - t0
-        res = StageResult(str(p), size, raw_size, sec, decoded=True,
+        res = StageResult(str(p), size, hdr.raw_size, sec, decoded=True,
                           verified=self.verify)
         logger.info("staged %s: %d -> %d bytes in %.3fs (%.2f GB/s raw)",
-                    p.name, size, raw_size, sec, res.gbps)
+                    p.name, size, hdr.raw_size, sec, res.gbps)
         return out, res
 
     def _decode(self, d_payload, idx: shardfmt.ShardIndex):

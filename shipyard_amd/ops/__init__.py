@@ -16,7 +16,6 @@ from __future__ import annotations
 
 import ctypes
 import os
-import os as _os
 from pathlib import Path
 from typing import Optional
 
@@ -312,7 +311,7 @@ def lz4_compress_blocks_gpu(data, block_raw: int,
     ``data``'s base: it must be contiguous and 16-byte aligned
     (ValueError before launch otherwise)."""
     if screen is None:
-        screen = _os.environ.get("SHIPYARD_LZ4C_SCREEN", "1") == "1"
+        screen = os.environ.get("SHIPYARD_LZ4C_SCREEN", "1") == "1"
 
     import torch
 
@@ -402,8 +401,53 @@ def gather_copy(src, src_off, dst, dst_off, lens):
     _check(rc, "sy_gather_copy")
 
 
-SHUFFLE_ELEM_SIZES = (2, 4, 8)
-SHUFFLE_BLOCK_ALIGN = 4096
+FILTER_ELEM_SIZES = (2, 4, 8)
+FILTER_BLOCK_ALIGN = 4096
+
+
+def _block_filter(name: str, entry: str, allow_in_place: bool, src, dst,
+                  block_raw: int, elem_size: int, inverse: bool) -> None:
+    """Argument rules and launch shared by the SYSHARD block filters:
+    the op ``name`` bound to the C entry point ``entry``, which takes
+    ``dst`` being ``src`` itself only with ``allow_in_place``.  Every
+    ValueError comes ahead of the device assert."""
+    import torch
+
+    for t, which in ((src, "src"), (dst, "dst")):
+        assert t.dtype == torch.uint8 and t.is_contiguous(), \
+            f"{name}: {which}"
+        if t.data_ptr() % 16:
+            raise ValueError(
+                f"{name}: {which} base pointer must be 16-byte "
+                f"aligned (tensor storage offset {t.storage_offset()}); "
+                "pass an aligned view or .clone() it")
+    n = src.numel()
+    if dst.numel() != n:
+        raise ValueError(f"{name}: src has {n} bytes but dst {dst.numel()}")
+    in_place = allow_in_place and src.data_ptr() == dst.data_ptr()
+    if n and not in_place and src.data_ptr() < dst.data_ptr() + n and \
+            dst.data_ptr() < src.data_ptr() + n:
+        raise ValueError(
+            f"{name}: src and dst overlap " +
+            ("partially (in place means the same base and length)"
+             if allow_in_place else "(this filter cannot run in place)"))
+    if elem_size not in FILTER_ELEM_SIZES:
+        raise ValueError(
+            f"{name}: elem_size={elem_size} not in {FILTER_ELEM_SIZES}")
+    if not 0 < block_raw < (1 << 32) or block_raw % FILTER_BLOCK_ALIGN:
+        raise ValueError(
+            f"{name}: block_raw={block_raw} must be a positive "
+            f"multiple of {FILTER_BLOCK_ALIGN} below 2**32")
+    assert src.is_cuda and dst.is_cuda and src.device == dst.device, \
+        f"{name}: CUDA tensors on one device"
+    if n == 0:
+        return
+    rc = getattr(_load(), entry)(
+        ctypes.c_void_p(src.data_ptr()), ctypes.c_void_p(dst.data_ptr()),
+        ctypes.c_uint64(n), ctypes.c_uint32(block_raw),
+        ctypes.c_uint32(elem_size), ctypes.c_int(int(bool(inverse))),
+        _stream())
+    _check(rc, entry)
 
 
 def byte_shuffle(src, dst, block_raw: int, elem_size: int,
@@ -421,48 +465,8 @@ def byte_shuffle(src, dst, block_raw: int, elem_size: int,
     multiple of 4096 below 2**32.  Each violation is a ValueError raised
     before any launch (and ahead of the device assert, so the rules are
     testable on hosts without a GPU)."""
-    import torch
-
-    for t, name in ((src, "src"), (dst, "dst")):
-        assert t.dtype == torch.uint8 and t.is_contiguous(), \
-            f"byte_shuffle: {name}"
-        if t.data_ptr() % 16:
-            raise ValueError(
-                f"byte_shuffle: {name} base pointer must be 16-byte "
-                f"aligned (tensor storage offset {t.storage_offset()}); "
-                "pass an aligned view or .clone() it")
-    n = src.numel()
-    if dst.numel() != n:
-        raise ValueError(
-            f"byte_shuffle: src has {n} bytes but dst {dst.numel()}")
-    if n and src.data_ptr() < dst.data_ptr() + n and \
-            dst.data_ptr() < src.data_ptr() + n:
-        raise ValueError(
-            "byte_shuffle: src and dst overlap (the transpose cannot "
-            "run in place)")
-    if elem_size not in SHUFFLE_ELEM_SIZES:
-        raise ValueError(
-            f"byte_shuffle: elem_size={elem_size} not in "
-            f"{SHUFFLE_ELEM_SIZES}")
-    if not 0 < block_raw < (1 << 32) or block_raw % SHUFFLE_BLOCK_ALIGN:
-        raise ValueError(
-            f"byte_shuffle: block_raw={block_raw} must be a positive "
-            f"multiple of {SHUFFLE_BLOCK_ALIGN} below 2**32")
-    assert src.is_cuda and dst.is_cuda and src.device == dst.device, \
-        "byte_shuffle: CUDA tensors on one device"
-    if n == 0:
-        return
-    lib = _load()
-    rc = lib.sy_byte_shuffle(
-        ctypes.c_void_p(src.data_ptr()), ctypes.c_void_p(dst.data_ptr()),
-        ctypes.c_uint64(n), ctypes.c_uint32(block_raw),
-        ctypes.c_uint32(elem_size), ctypes.c_int(int(bool(inverse))),
-        _stream())
-    _check(rc, "sy_byte_shuffle")
-
-
-DELTA_ELEM_SIZES = (2, 4, 8)
-DELTA_BLOCK_ALIGN = 4096
+    _block_filter("byte_shuffle", "sy_byte_shuffle", False, src, dst,
+                  block_raw, elem_size, inverse)
 
 
 def delta_filter(src, dst, block_raw: int, elem_size: int,
@@ -487,50 +491,13 @@ def delta_filter(src, dst, block_raw: int, elem_size: int,
 
     One workgroup decodes one block from start to end, so a buffer of a
     few very large blocks uses only a few CUs."""
-    import torch
-
-    for t, name in ((src, "src"), (dst, "dst")):
-        assert t.dtype == torch.uint8 and t.is_contiguous(), \
-            f"delta_filter: {name}"
-        if t.data_ptr() % 16:
-            raise ValueError(
-                f"delta_filter: {name} base pointer must be 16-byte "
-                f"aligned (tensor storage offset {t.storage_offset()}); "
-                "pass an aligned view or .clone() it")
-    n = src.numel()
-    if dst.numel() != n:
-        raise ValueError(
-            f"delta_filter: src has {n} bytes but dst {dst.numel()}")
-    if n and src.data_ptr() != dst.data_ptr() and \
-            src.data_ptr() < dst.data_ptr() + n and \
-            dst.data_ptr() < src.data_ptr() + n:
-        raise ValueError(
-            "delta_filter: src and dst overlap partially (in place "
-            "means the same base and length)")
-    if elem_size not in DELTA_ELEM_SIZES:
-        raise ValueError(
-            f"delta_filter: elem_size={elem_size} not in "
-            f"{DELTA_ELEM_SIZES}")
-    if not 0 < block_raw < (1 << 32) or block_raw % DELTA_BLOCK_ALIGN:
-        raise ValueError(
-            f"delta_filter: block_raw={block_raw} must be a positive "
-            f"multiple of {DELTA_BLOCK_ALIGN} below 2**32")
-    assert src.is_cuda and dst.is_cuda and src.device == dst.device, \
-        "delta_filter: CUDA tensors on one device"
-    if n == 0:
-        return
-    lib = _load()
-    rc = lib.sy_delta_filter(
-        ctypes.c_void_p(src.data_ptr()), ctypes.c_void_p(dst.data_ptr()),
-        ctypes.c_uint64(n), ctypes.c_uint32(block_raw),
-        ctypes.c_uint32(elem_size), ctypes.c_int(int(bool(inverse))),
-        _stream())
-    _check(rc, "sy_delta_filter")
+    _block_filter("delta_filter", "sy_delta_filter", True, src, dst,
+                  block_raw, elem_size, inverse)
 
 
 def _env_atoi(name: str, default: int) -> int:
     """The value lz4_decode.hip's getenv + atoi gives for ``name``."""
-    e = _os.environ.get(name)
+    e = os.environ.get(name)
     if e is None:
         return default
     try:
@@ -567,8 +534,6 @@ def lz4_decode_blocks(comp, in_off, in_len, out, out_off, out_len,
     uint4 from ``comp + offset``, so there a misaligned ``comp`` base
     raises ValueError before launch as well.
     """
-    import os as _os
-
     import torch
 
     if out.data_ptr() % 16:
@@ -576,7 +541,7 @@ def lz4_decode_blocks(comp, in_off, in_len, out, out_off, out_len,
             "lz4_decode_blocks: out base pointer must be 16-byte "
             f"aligned (tensor storage offset {out.storage_offset()})")
     if pc is None:
-        pc = _os.environ.get("SHIPYARD_LZ4_PC", "0") == "1"
+        pc = os.environ.get("SHIPYARD_LZ4_PC", "0") == "1"
     if comp.data_ptr() % 16 and (pc or _lz4_staged_by_env()):
         raise ValueError(
             "lz4_decode_blocks: comp base pointer must be 16-byte "
@@ -631,11 +596,9 @@ def stage_file_native(path, dst, file_off: int = 0,
     """Native C++ staging pipeline: pread (O_DIRECT when possible) ->
     pinned ring -> hipMemcpyAsync into the uint8 CUDA tensor ``dst``.
     Returns pipeline seconds."""
-    import os as _os
-
     lib = _load()
     if n_bytes is None:
-        n_bytes = _os.path.getsize(path) - file_off
+        n_bytes = os.path.getsize(path) - file_off
     assert dst.numel() >= n_bytes
     secs = ctypes.c_double(0.0)
     rc = lib.sy_stage_file(
@@ -645,7 +608,7 @@ def stage_file_native(path, dst, file_off: int = 0,
         _stream(), ctypes.byref(secs))
     if rc != 0:
         raise RuntimeError(f"sy_stage_file failed rc={rc} "
-                           f"({_os.strerror(-rc) if rc < 0 else 'hip'})")
+                           f"({os.strerror(-rc) if rc < 0 else 'hip'})")
     return secs.value
 
 

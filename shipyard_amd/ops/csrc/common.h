@@ -20,3 +20,31 @@ static inline int sy_check(hipError_t e) { return static_cast<int>(e); }
 #ifndef SY_WAVE
 #define SY_WAVE 64
 #endif
+
+// Host side of the SYSHARD block filters (byte_shuffle.hip,
+// delta_filter.hip): one launch walks a buffer of block_raw-sized blocks
+// whose last block may be short.
+
+// What the exported wrappers accept: blocks made of whole 4 KiB tiles,
+// elements of 2, 4 or 8 bytes.
+static inline bool sy_filter_args_ok(uint32_t block_raw, uint32_t elem_size) {
+  return block_raw != 0 && block_raw % 4096 == 0 &&
+         (elem_size == 2 || elem_size == 4 || elem_size == 8);
+}
+
+struct SyBlockSplit {
+  uint64_t n_full;    // blocks of exactly block_raw bytes
+  uint32_t tail_len;  // bytes of the ragged final block, 0 if none
+};
+
+static inline SyBlockSplit sy_block_split(uint64_t n_bytes,
+                                          uint32_t block_raw) {
+  const uint64_t n_full = n_bytes / block_raw;
+  return {n_full, static_cast<uint32_t>(n_bytes - n_full * block_raw)};
+}
+
+// capped grid + grid-stride loop: 32 workgroups per CU's worth
+static inline uint32_t sy_capped_grid(uint64_t n_work) {
+  const uint32_t cap = 8192;
+  return n_work < cap ? static_cast<uint32_t>(n_work) : cap;
+}

@@ -308,14 +308,9 @@ __global__ __launch_bounds__(kThreads) void delta_filter_kernel(
 template <typename T>
 int launch(const uint8_t* src, uint8_t* dst, uint64_t n_bytes,
            uint32_t block_raw, int inverse, hipStream_t stream) {
-  const uint64_t n_full = n_bytes / block_raw;
-  const uint32_t tail_len =
-      static_cast<uint32_t>(n_bytes - n_full * block_raw);
+  const auto [n_full, tail_len] = sy_block_split(n_bytes, block_raw);
   const uint64_t n_work = n_full + (tail_len ? 1 : 0);
-  // capped grid + grid-stride loop over blocks: 32 workgroups per CU's
-  // worth, as in byte_shuffle.hip
-  const uint32_t cap = 8192;
-  const uint32_t grid = n_work < cap ? static_cast<uint32_t>(n_work) : cap;
+  const uint32_t grid = sy_capped_grid(n_work);  // grid-stride over blocks
   if (inverse)
     hipLaunchKernelGGL((delta_filter_kernel<T, true>), dim3(grid),
                        dim3(kThreads), 0, stream, src, dst, n_full, block_raw,
@@ -337,9 +332,7 @@ SY_EXPORT int sy_delta_filter(const void* d_src, void* d_dst,
                               uint64_t n_bytes, uint32_t block_raw,
                               uint32_t elem_size, int inverse,
                               hipStream_t stream) {
-  if (block_raw == 0 || block_raw % kTileBytes)
-    return sy_check(hipErrorInvalidValue);
-  if (elem_size != 2 && elem_size != 4 && elem_size != 8)
+  if (!sy_filter_args_ok(block_raw, elem_size))
     return sy_check(hipErrorInvalidValue);
   if (n_bytes == 0) return 0;
   const uint8_t* s = static_cast<const uint8_t*>(d_src);

@@ -15,8 +15,8 @@ torch = pytest.importorskip("torch")
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from shard_delta_stub_ops import (FilterOps, decode_index,  # noqa: E402
-                                  decode_packed)
+from shard_stub_ops import (FilterOps, decode_index_aligned,  # noqa: E402
+                            decode_packed)
 
 from shipyard_amd import ops  # noqa: E402
 from shipyard_amd.data import shardfmt  # noqa: E402
@@ -361,7 +361,7 @@ def test_decode_device_corrupt_index_launches_nothing():
     table["comp_off"][1] += 8  # misaligned block start
     fake = FilterOps()
     with pytest.raises(ValueError, match="16-byte aligned"):
-        decode_index(shardfmt.ShardIndex(
+        decode_index_aligned(shardfmt.ShardIndex(
             idx.block_raw, idx.raw_size, 0, table=table, delta_elem=8,
             shuffle_elem=8), payload, fake)
     assert fake.launches == 0
@@ -369,13 +369,13 @@ def test_decode_device_corrupt_index_launches_nothing():
     table = idx.table.copy()
     table["comp_len"][-1] = len(payload) + 1  # past the payload
     with pytest.raises(ValueError):
-        decode_index(shardfmt.ShardIndex(
+        decode_index_aligned(shardfmt.ShardIndex(
             idx.block_raw, idx.raw_size, 0, table=table, delta_elem=8),
             payload, fake)
     assert fake.launches == 0
 
     with pytest.raises(ValueError, match="delta_elem"):
-        decode_index(shardfmt.ShardIndex(
+        decode_index_aligned(shardfmt.ShardIndex(
             idx.block_raw, idx.raw_size, 0, table=idx.table, delta_elem=3),
             payload, fake)
     assert fake.launches == 0

@@ -6,7 +6,6 @@ The device kernel itself is covered by tests/test_shuffle_gpu (-m gpu)."""
 import os
 import struct
 import sys
-from unittest import mock
 
 import numpy as np
 import pytest
@@ -15,7 +14,7 @@ torch = pytest.importorskip("torch")
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from shard_stub_ops import CpuOps  # noqa: E402
+from shard_stub_ops import FilterOps, decode_packed  # noqa: E402
 
 from shipyard_amd import ops  # noqa: E402
 from shipyard_amd.data import shardfmt  # noqa: E402
@@ -193,35 +192,6 @@ def test_byte_shuffle_guards_fire_without_a_device():
     assert not buf.any()  # nothing ran
 
 
-class _ShuffleOps(CpuOps):
-    """CpuOps plus a strict stand-in for ops.byte_shuffle."""
-
-    def byte_shuffle(self, src, dst, block_raw, elem_size, inverse=False):
-        assert src.dtype == torch.uint8 and dst.dtype == torch.uint8
-        assert src.numel() == dst.numel()
-        assert block_raw % 4096 == 0 and elem_size in (2, 4, 8)
-        s0, d0, n = src.data_ptr(), dst.data_ptr(), src.numel()
-        assert s0 + n <= d0 or d0 + n <= s0, "aliasing output"
-        self.calls.append(("shuffle", n))
-        out = shardfmt.shuffle_blocks_numpy(
-            bytes(src.numpy().tobytes()), block_raw, elem_size, inverse)
-        dst.copy_(torch.frombuffer(bytearray(out), dtype=torch.uint8))
-
-
-def _decode_stubbed(packed, fake):
-    idx = shardfmt.read_index(packed)
-    d_comp = torch.frombuffer(bytearray(packed[idx.payload_off:]),
-                              dtype=torch.uint8)
-    with mock.patch("shipyard_amd.ops.gather_copy", fake.gather_copy), \
-         mock.patch("shipyard_amd.ops.lz4_decode_blocks",
-                    fake.lz4_decode_blocks), \
-         mock.patch("shipyard_amd.ops.lz4_all_ok", fake.lz4_all_ok), \
-         mock.patch("shipyard_amd.ops.crc32c_chunks", fake.crc32c_chunks), \
-         mock.patch("shipyard_amd.ops.byte_shuffle", fake.byte_shuffle):
-        out = shardfmt.decode_device(d_comp, idx, torch.device("cpu"))
-    return out, d_comp
-
-
 @pytest.mark.parametrize("compress", [True, False])
 def test_decode_device_orchestration(compress):
     """Host side of the GPU reader: one unshuffle launch after decode,
@@ -229,8 +199,8 @@ def test_decode_device_orchestration(compress):
     x = _bytes(2 * 8192, seed=3) + os.urandom(8192) + _bytes(1001, seed=4)
     packed = shardfmt.pack(x, block_raw=8192, compress=compress,
                            shuffle_elem=4)
-    fake = _ShuffleOps()
-    out, d_comp = _decode_stubbed(packed, fake)
+    fake = FilterOps()
+    out, d_comp = decode_packed(packed, fake)
     assert bytes(out.numpy().tobytes()) == x
     kinds = [k for k, _ in fake.calls]
     assert kinds.count("shuffle") == 1
@@ -243,7 +213,7 @@ def test_decode_device_orchestration(compress):
     bad = bytearray(packed)
     bad[shardfmt.read_index(packed).payload_off + 3] ^= 0x40
     with pytest.raises(ValueError, match="CRC mismatch"):
-        _decode_stubbed(bytes(bad), _ShuffleOps())
+        decode_packed(bytes(bad), FilterOps())
 
 
 def test_object_store_round_trip(tmp_path):
