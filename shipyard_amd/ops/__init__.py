@@ -496,7 +496,8 @@ def delta_filter(src, dst, block_raw: int, elem_size: int,
 
 
 def _env_atoi(name: str, default: int) -> int:
-    """The value lz4_decode.hip's getenv + atoi gives for ``name``."""
+    """The value common.h's sy_env_atoi (getenv + atoi) gives for
+    ``name`` in lz4_decode.hip."""
     e = os.environ.get(name)
     if e is None:
         return default
@@ -548,7 +549,8 @@ def lz4_decode_blocks(comp, in_off, in_len, out, out_off, out_len,
             "aligned on the producer/consumer and staged paths (tensor "
             f"storage offset {comp.storage_offset()})")
     lib = _load()
-    fn = lib.sy_lz4_decode_blocks_pc if pc else lib.sy_lz4_decode_blocks
+    entry = "sy_lz4_decode_blocks_pc" if pc else "sy_lz4_decode_blocks"
+    fn = getattr(lib, entry)
     n_blocks = in_off.numel()
     status = torch.empty(n_blocks, dtype=torch.uint32, device=comp.device)
     rc = fn(
@@ -557,7 +559,7 @@ def lz4_decode_blocks(comp, in_off, in_len, out, out_off, out_len,
         ctypes.c_void_p(out_off.data_ptr()), ctypes.c_void_p(out_len.data_ptr()),
         ctypes.c_void_p(status.data_ptr()), ctypes.c_uint32(n_blocks),
         ctypes.c_uint32(raw_cap), _stream())
-    _check(rc, "sy_lz4_decode_blocks")
+    _check(rc, entry)
     return status
 
 

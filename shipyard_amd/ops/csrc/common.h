@@ -9,6 +9,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cstdlib>
+#include <type_traits>
+
 #define SY_EXPORT extern "C" __attribute__((visibility("default")))
 
 // Error contract: every entry point returns a hipError_t-compatible int
@@ -20,6 +23,30 @@ static inline int sy_check(hipError_t e) { return static_cast<int>(e); }
 #ifndef SY_WAVE
 #define SY_WAVE 64
 #endif
+
+// Integer knob from the environment with C atoi semantics (leading
+// integer, 0 for garbage); `unset` when the variable is absent.  Callers
+// keep the result in a function-local static so each variable is read
+// once per process.  ops._env_atoi mirrors this in Python.
+static inline int sy_env_atoi(const char* name, int unset) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : unset;
+}
+
+// Host side of the LZ4 kernels (lz4_decode.hip, lz4_compress_gpu.hip):
+// each kernel is compiled for a ladder of RAWCAP rungs (LDS bytes per
+// block, so occupancy).  Calls f(std::integral_constant<int, CAP>{}) for
+// the smallest CAP >= raw_cap and returns its result; CAPS ascend.
+// Returns -22 (EINVAL) when raw_cap is above the top rung: f is not
+// called and nothing is launched.
+template <int... CAPS, class F>
+static inline int sy_dispatch_rung(uint32_t raw_cap, F&& f) {
+  int rc = -22;
+  (void)((raw_cap <= static_cast<uint32_t>(CAPS) &&
+          ((rc = f(std::integral_constant<int, CAPS>{})), true)) ||
+         ...);
+  return rc;
+}
 
 // Host side of the SYSHARD block filters (byte_shuffle.hip,
 // delta_filter.hip): one launch walks a buffer of block_raw-sized blocks

@@ -22,69 +22,110 @@
 // Output: slotted buffer (blk * stride) + out_lens[blk] = compressed
 // size, or 0 when not smaller than raw (caller stores the block raw —
 // same contract as the CPU entry point).
+//
+// Two kernels, the serial greedy matcher (lz4_compress_kernel) and the
+// wave-screen matcher (lz4_compress_screen_kernel), share the staging,
+// table clear, unaligned read and match extension below and the host
+// dispatch; each keeps its matcher loop and its own copy of the emit
+// lambdas (see the note there).
 
 #include "common.h"
 
 namespace {
 
+constexpr uint32_t kHashSlots = 4096;
+
 __device__ __forceinline__ uint32_t hash4(uint32_t v) {
   return (v * 2654435761u) >> 20;  // 12-bit table
 }
 
+// unaligned 32-bit read from the LDS copy: two aligned words +
+// funnel shift (v_alignbit) — ONE LDS round trip on the chain
+// instead of four serial byte loads
+__device__ __forceinline__ uint32_t lds_rd32(const uint8_t* sbuf,
+                                             uint32_t off) {
+  const uint32_t* sw = reinterpret_cast<const uint32_t*>(sbuf);
+  const uint32_t lo = sw[off >> 2], hi = sw[(off >> 2) + 1];
+  const uint32_t sh = (off & 3u) * 8u;
+  return sh ? ((lo >> sh) | (hi << (32u - sh))) : lo;
+}
+
+// stage the source block into LDS (coalesced 16 B/lane; in_off is
+// block_raw-aligned from the wrapper, so uint4 loads are aligned;
+// the ragged tail copies bytewise so the last block never reads
+// past the input tensor)
+__device__ __forceinline__ void stage_block(uint8_t* sbuf,
+                                            const uint8_t* gsrc, uint32_t n,
+                                            int lane) {
+  const uint4* g4 = reinterpret_cast<const uint4*>(gsrc);
+  uint4* s4 = reinterpret_cast<uint4*>(sbuf);
+  const uint32_t nfull = n >> 4;
+  for (uint32_t i = lane; i < nfull; i += SY_WAVE) s4[i] = g4[i];
+  for (uint32_t i = (nfull << 4) + lane; i < n; i += SY_WAVE)
+    sbuf[i] = gsrc[i];
+}
+
+// clear the hash table (64 lanes x 64 entries); T is uint16_t in the
+// serial matcher, uint32_t (for atomicMax) in the screen matcher
+template <class T>
+__device__ __forceinline__ void clear_table(T* ht, int lane) {
+  for (uint32_t i = lane; i < kHashSlots; i += SY_WAVE) ht[i] = 0;
+}
+
+// wave-parallel match extension: 64 B compared per ballot round.
+// The 4-byte match at src[r] / src[pos] is already known; returns the
+// full match length, which stops short of match_limit.
+__device__ __forceinline__ uint32_t extend_match(const uint8_t* src,
+                                                 uint32_t r, uint32_t pos,
+                                                 uint32_t match_limit,
+                                                 int lane) {
+  uint32_t mlen = 4;
+  for (;;) {
+    const uint32_t i = mlen + (uint32_t)lane;
+    const bool ok = (pos + i < match_limit) && src[r + i] == src[pos + i];
+    const uint64_t mask = __ballot(ok);
+    const uint32_t run =
+        (~mask == 0ull) ? 64u : (uint32_t)(__ffsll((long long)~mask) - 1);
+    mlen += run;
+    if (run < 64u) break;
+  }
+  return mlen;
+}
+
+// Serial greedy matcher: the CPU policy exactly, one scanned position
+// per LDS round trip.
 template <int RAWCAP>
 __global__ __launch_bounds__(SY_WAVE) void lz4_compress_kernel(
     const uint8_t* __restrict__ data, const uint64_t* __restrict__ in_off,
     const uint32_t* __restrict__ in_len, uint8_t* __restrict__ out,
     uint64_t stride, uint32_t* __restrict__ out_lens, uint32_t n_blocks) {
-  __shared__ uint16_t ht[4096];
+  __shared__ uint16_t ht[kHashSlots];
   __shared__ uint8_t sbuf[RAWCAP + 16];
 
   const int lane = threadIdx.x;
-  const uint32_t* sw = reinterpret_cast<const uint32_t*>(sbuf);
-  // unaligned 32-bit read from the LDS copy: two aligned words +
-  // funnel shift (v_alignbit) — ONE LDS round trip on the chain
-  // instead of four serial byte loads
-  auto rd32g = [&](const uint8_t* p) -> uint32_t {
-    const uint32_t off = (uint32_t)(p - sbuf);
-    const uint32_t lo = sw[off >> 2], hi = sw[(off >> 2) + 1];
-    const uint32_t sh = (off & 3u) * 8u;
-    return sh ? ((lo >> sh) | (hi << (32u - sh))) : lo;
-  };
+  const uint8_t* src = sbuf;
 
   for (uint32_t blk = blockIdx.x; blk < n_blocks; blk += gridDim.x) {
-    const uint8_t* gsrc = data + in_off[blk];
     const uint32_t n = in_len[blk];
-    const uint32_t cap = n;  // emit caps at raw size (else stored)
-    uint8_t* dstbuf = out + (uint64_t)blk * stride;
     if (n > (uint32_t)RAWCAP) {  // host routes by raw_cap; belt+braces
       if (lane == 0) out_lens[blk] = 0;
       continue;
     }
-
-    // stage the source block into LDS (coalesced 16 B/lane; in_off is
-    // block_raw-aligned from the wrapper, so uint4 loads are aligned;
-    // the ragged tail copies bytewise so the last block never reads
-    // past the input tensor)
-    {
-      const uint4* g4 = reinterpret_cast<const uint4*>(gsrc);
-      uint4* s4 = reinterpret_cast<uint4*>(sbuf);
-      const uint32_t nfull = n >> 4;
-      for (uint32_t i = lane; i < nfull; i += SY_WAVE) s4[i] = g4[i];
-      for (uint32_t i = (nfull << 4) + lane; i < n; i += SY_WAVE)
-        sbuf[i] = gsrc[i];
-    }
-    const uint8_t* src = sbuf;
-
-    // clear the hash table (64 lanes x 64 entries)
-    for (uint32_t i = lane; i < 4096; i += SY_WAVE) ht[i] = 0;
+    stage_block(sbuf, data + in_off[blk], n, lane);
+    clear_table(ht, lane);
     __builtin_amdgcn_s_waitcnt(0);
 
     uint32_t opos = 0;
     bool fail = false;
+    uint8_t* dstbuf = out + (uint64_t)blk * stride;
+    const uint32_t cap = n;  // emit caps at raw size (else stored)
 
     // emit helpers run in UNIFORM control flow (every lane computes
     // the same scalar state; same-address same-value LDS writes are
-    // benign, but we predicate on lane 0 to keep LDS traffic down)
+    // benign, but we predicate on lane 0 to keep LDS traffic down).
+    // They stay lambdas over kernel locals, one copy per kernel: as
+    // methods of a shared struct the compiler keeps opos/fail in
+    // vector registers and the 8 KiB and 64 KiB rows measured slower.
     auto emit_byte = [&](uint8_t b) {
       if (opos >= cap) { fail = true; return; }
       if (lane == 0) dstbuf[opos] = b;
@@ -117,36 +158,24 @@ __global__ __launch_bounds__(SY_WAVE) void lz4_compress_kernel(
       emit_byte((uint8_t)(offset >> 8));
       if (!fail && ml >= 15) emit_len(ml - 15);
     };
-
     if (n >= 13) {
       const uint32_t mflimit = n - 12;
       const uint32_t match_limit = n - 5;
       uint32_t anchor = 0, pos = 0;
       while (pos <= mflimit && !fail) {
-        const uint32_t h = hash4(rd32g(src + pos));
+        const uint32_t h = hash4(lds_rd32(sbuf, pos));
         const uint32_t ref = (uint32_t)ht[h];  // pos+1 encoding
         ht[h] = (uint16_t)(pos + 1);
         if (ref != 0 && ref - 1 < pos && pos - (ref - 1) <= 65535 &&
-            rd32g(src + (ref - 1)) == rd32g(src + pos)) {
+            lds_rd32(sbuf, ref - 1) == lds_rd32(sbuf, pos)) {
           const uint32_t r = ref - 1;
-          // wave-parallel extension: 64 B compared per ballot round
-          uint32_t mlen = 4;
-          for (;;) {
-            const uint32_t i = mlen + (uint32_t)lane;
-            const bool ok = (pos + i < match_limit) &&
-                            src[r + i] == src[pos + i];
-            const uint64_t mask = __ballot(ok);
-            const uint32_t run =
-                (~mask == 0ull) ? 64u : (uint32_t)(__ffsll((long long)~mask) - 1);
-            mlen += run;
-            if (run < 64u) break;
-          }
+          const uint32_t mlen = extend_match(src, r, pos, match_limit, lane);
           emit_seq(anchor, pos, pos - r, mlen);
           pos += mlen;
           anchor = pos;
           // re-prime inside the skipped span (matches CPU matcher)
           if (pos <= mflimit)
-            ht[hash4(rd32g(src + pos - 2))] = (uint16_t)(pos - 1);
+            ht[hash4(lds_rd32(sbuf, pos - 2))] = (uint16_t)(pos - 1);
         } else {
           ++pos;
         }
@@ -162,64 +191,51 @@ __global__ __launch_bounds__(SY_WAVE) void lz4_compress_kernel(
   }
 }
 
-}  // namespace
-
 // ---------------------------------------------------------------------
 // v2 "wave-screen" matcher: instead of one serial LDS round trip per
 // scanned position, the wave screens 64 positions at once — parallel
 // rd32 + hash + table gather, ballot for the first candidate — then
 // inserts the scanned span with ds atomicMax (deterministic: max ==
 // most-recent position regardless of write order).  Match extension
-// and emission reuse the v1 wave code.  Semantics: a valid greedy-LZ4
-// stream, but NOT byte-identical to v1 — candidates whose source lies
-// inside the current 64-position batch are invisible (their inserts
-// land after the screen), so some short-range matches shift by a
-// batch.  Tests assert decode-roundtrip + ratio bounds instead.
+// and emission are the shared wave code above.  Semantics: a valid
+// greedy-LZ4 stream, but NOT byte-identical to v1 — candidates whose
+// source lies inside the current 64-position batch are invisible
+// (their inserts land after the screen), so some short-range matches
+// shift by a batch.  Tests assert decode-roundtrip + ratio bounds
+// instead.
 // ---------------------------------------------------------------------
-
-namespace {
-
 template <int RAWCAP>
 __global__ __launch_bounds__(SY_WAVE) void lz4_compress_screen_kernel(
     const uint8_t* __restrict__ data, const uint64_t* __restrict__ in_off,
     const uint32_t* __restrict__ in_len, uint8_t* __restrict__ out,
     uint64_t stride, uint32_t* __restrict__ out_lens, uint32_t n_blocks) {
-  __shared__ uint32_t ht[4096];  // u32 for atomicMax
+  __shared__ uint32_t ht[kHashSlots];  // u32 for atomicMax
   __shared__ uint8_t sbuf[RAWCAP + 16];
 
   const int lane = threadIdx.x;
-  const uint32_t* sw = reinterpret_cast<const uint32_t*>(sbuf);
-  auto rd32 = [&](uint32_t off) -> uint32_t {
-    const uint32_t lo = sw[off >> 2], hi = sw[(off >> 2) + 1];
-    const uint32_t sh = (off & 3u) * 8u;
-    return sh ? ((lo >> sh) | (hi << (32u - sh))) : lo;
-  };
+  const uint8_t* src = sbuf;
 
   for (uint32_t blk = blockIdx.x; blk < n_blocks; blk += gridDim.x) {
-    const uint8_t* gsrc = data + in_off[blk];
     const uint32_t n = in_len[blk];
-    const uint32_t cap = n;
-    uint8_t* dstbuf = out + (uint64_t)blk * stride;
-    if (n > (uint32_t)RAWCAP) {
+    if (n > (uint32_t)RAWCAP) {  // host routes by raw_cap; belt+braces
       if (lane == 0) out_lens[blk] = 0;
       continue;
     }
-
-    {
-      const uint4* g4 = reinterpret_cast<const uint4*>(gsrc);
-      uint4* s4 = reinterpret_cast<uint4*>(sbuf);
-      const uint32_t nfull = n >> 4;
-      for (uint32_t i = lane; i < nfull; i += SY_WAVE) s4[i] = g4[i];
-      for (uint32_t i = (nfull << 4) + lane; i < n; i += SY_WAVE)
-        sbuf[i] = gsrc[i];
-    }
-    for (uint32_t i = lane; i < 4096; i += SY_WAVE) ht[i] = 0;
+    stage_block(sbuf, data + in_off[blk], n, lane);
+    clear_table(ht, lane);
     __builtin_amdgcn_s_waitcnt(0);
 
     uint32_t opos = 0;
     bool fail = false;
-    const uint8_t* src = sbuf;
+    uint8_t* dstbuf = out + (uint64_t)blk * stride;
+    const uint32_t cap = n;  // emit caps at raw size (else stored)
 
+    // emit helpers run in UNIFORM control flow (every lane computes
+    // the same scalar state; same-address same-value LDS writes are
+    // benign, but we predicate on lane 0 to keep LDS traffic down).
+    // They stay lambdas over kernel locals, one copy per kernel: as
+    // methods of a shared struct the compiler keeps opos/fail in
+    // vector registers and the 8 KiB and 64 KiB rows measured slower.
     auto emit_byte = [&](uint8_t b) {
       if (opos >= cap) { fail = true; return; }
       if (lane == 0) dstbuf[opos] = b;
@@ -252,7 +268,6 @@ __global__ __launch_bounds__(SY_WAVE) void lz4_compress_screen_kernel(
       emit_byte((uint8_t)(offset >> 8));
       if (!fail && ml >= 15) emit_len(ml - 15);
     };
-
     if (n >= 13) {
       const uint32_t mflimit = n - 12;
       const uint32_t match_limit = n - 5;
@@ -264,10 +279,10 @@ __global__ __launch_bounds__(SY_WAVE) void lz4_compress_screen_kernel(
         uint32_t v = 0, h = 0, ref = 0;
         bool cand = false;
         if (in_range) {
-          v = rd32(p);
+          v = lds_rd32(sbuf, p);
           h = hash4(v);
           ref = ht[h];
-          cand = ref != 0 && ref - 1 < p && rd32(ref - 1) == v;
+          cand = ref != 0 && ref - 1 < p && lds_rd32(sbuf, ref - 1) == v;
         }
         const uint64_t mask = __ballot(cand);
         const uint32_t j = mask ? (uint32_t)(__ffsll((long long)mask)
@@ -283,24 +298,13 @@ __global__ __launch_bounds__(SY_WAVE) void lz4_compress_screen_kernel(
         }
         const uint32_t pstar = pos + j;
         const uint32_t rstar = __shfl(ref, (int)j) - 1;
-        // ---- wave-parallel extension from pstar/rstar ----
-        uint32_t mlen = 4;
-        for (;;) {
-          const uint32_t i = mlen + (uint32_t)lane;
-          const bool ok = (pstar + i < match_limit) &&
-                          src[rstar + i] == src[pstar + i];
-          const uint64_t m2 = __ballot(ok);
-          const uint32_t run =
-              (~m2 == 0ull) ? 64u
-                            : (uint32_t)(__ffsll((long long)~m2) - 1);
-          mlen += run;
-          if (run < 64u) break;
-        }
+        const uint32_t mlen =
+            extend_match(src, rstar, pstar, match_limit, lane);
         emit_seq(anchor, pstar, pstar - rstar, mlen);
         pos = pstar + mlen;
         anchor = pos;
         if (pos <= mflimit) {  // reprime like the serial matcher
-          atomicMax(&ht[hash4(rd32(pos - 2))], pos - 1);
+          atomicMax(&ht[hash4(lds_rd32(sbuf, pos - 2))], pos - 1);
         }
       }
       if (!fail) emit_seq(anchor, n, 0, 0);
@@ -314,75 +318,53 @@ __global__ __launch_bounds__(SY_WAVE) void lz4_compress_screen_kernel(
   }
 }
 
-}  // namespace
+// Kernel families for the shared host entry: rung -> instantiation.
+struct SerialMatcher {
+  template <int CAP>
+  static auto kernel() { return lz4_compress_kernel<CAP>; }
+};
+struct ScreenMatcher {
+  template <int CAP>
+  static auto kernel() { return lz4_compress_screen_kernel<CAP>; }
+};
 
-SY_EXPORT int sy_lz4_compress_blocks_gpu2(
-    const void* d_data, const uint64_t* d_in_off, const uint32_t* d_in_len,
-    void* d_out, uint64_t stride, uint32_t* d_out_lens, uint32_t n_blocks,
-    uint32_t raw_cap, hipStream_t stream) {
+template <class Family>
+int compress_blocks(const void* d_data, const uint64_t* d_in_off,
+                    const uint32_t* d_in_len, void* d_out, uint64_t stride,
+                    uint32_t* d_out_lens, uint32_t n_blocks,
+                    uint32_t raw_cap, hipStream_t stream) {
+  // nothing to compress: success without a launch, whatever raw_cap is
   if (n_blocks == 0) return 0;
-  if (raw_cap > 64 * 1024) return -22;
-  uint32_t grid = n_blocks < (1u << 20) ? n_blocks : (1u << 20);
-  const uint8_t* d = static_cast<const uint8_t*>(d_data);
-  uint8_t* o = static_cast<uint8_t*>(d_out);
-  if (raw_cap <= 4 * 1024) {
-    hipLaunchKernelGGL((lz4_compress_screen_kernel<4 * 1024>),
-                       dim3(grid), dim3(SY_WAVE), 0, stream, d,
-                       d_in_off, d_in_len, o, stride, d_out_lens,
-                       n_blocks);
-  } else if (raw_cap <= 8 * 1024) {
-    hipLaunchKernelGGL((lz4_compress_screen_kernel<8 * 1024>),
-                       dim3(grid), dim3(SY_WAVE), 0, stream, d,
-                       d_in_off, d_in_len, o, stride, d_out_lens,
-                       n_blocks);
-  } else if (raw_cap <= 16 * 1024) {
-    hipLaunchKernelGGL((lz4_compress_screen_kernel<16 * 1024>),
-                       dim3(grid), dim3(SY_WAVE), 0, stream, d,
-                       d_in_off, d_in_len, o, stride, d_out_lens,
-                       n_blocks);
-  } else if (raw_cap <= 32 * 1024) {
-    hipLaunchKernelGGL((lz4_compress_screen_kernel<32 * 1024>),
-                       dim3(grid), dim3(SY_WAVE), 0, stream, d,
-                       d_in_off, d_in_len, o, stride, d_out_lens,
-                       n_blocks);
-  } else {
-    hipLaunchKernelGGL((lz4_compress_screen_kernel<64 * 1024>),
-                       dim3(grid), dim3(SY_WAVE), 0, stream, d,
-                       d_in_off, d_in_len, o, stride, d_out_lens,
-                       n_blocks);
-  }
-  return sy_check(hipGetLastError());
+  const uint32_t grid = n_blocks < (1u << 20) ? n_blocks : (1u << 20);
+  // raw_cap > 64 KiB is -22: the serial matcher's table holds u16
+  // positions, and neither family has a larger rung.
+  return sy_dispatch_rung<4 * 1024, 8 * 1024, 16 * 1024, 32 * 1024,
+                          64 * 1024>(raw_cap, [&](auto cap) {
+    hipLaunchKernelGGL(Family::template kernel<decltype(cap)::value>(),
+                       dim3(grid), dim3(SY_WAVE), 0, stream,
+                       static_cast<const uint8_t*>(d_data), d_in_off,
+                       d_in_len, static_cast<uint8_t*>(d_out), stride,
+                       d_out_lens, n_blocks);
+    return sy_check(hipGetLastError());
+  });
 }
+
+}  // namespace
 
 SY_EXPORT int sy_lz4_compress_blocks_gpu(
     const void* d_data, const uint64_t* d_in_off, const uint32_t* d_in_len,
     void* d_out, uint64_t stride, uint32_t* d_out_lens, uint32_t n_blocks,
     uint32_t raw_cap, hipStream_t stream) {
-  if (n_blocks == 0) return 0;
-  if (raw_cap > 64 * 1024) return -22;  // u16 hash-table positions
-  uint32_t grid = n_blocks < (1u << 20) ? n_blocks : (1u << 20);
-  const uint8_t* d = static_cast<const uint8_t*>(d_data);
-  uint8_t* o = static_cast<uint8_t*>(d_out);
-  if (raw_cap <= 4 * 1024) {
-    hipLaunchKernelGGL((lz4_compress_kernel<4 * 1024>), dim3(grid),
-                       dim3(SY_WAVE), 0, stream, d, d_in_off, d_in_len,
-                       o, stride, d_out_lens, n_blocks);
-  } else if (raw_cap <= 8 * 1024) {
-    hipLaunchKernelGGL((lz4_compress_kernel<8 * 1024>), dim3(grid),
-                       dim3(SY_WAVE), 0, stream, d, d_in_off, d_in_len,
-                       o, stride, d_out_lens, n_blocks);
-  } else if (raw_cap <= 16 * 1024) {
-    hipLaunchKernelGGL((lz4_compress_kernel<16 * 1024>), dim3(grid),
-                       dim3(SY_WAVE), 0, stream, d, d_in_off, d_in_len,
-                       o, stride, d_out_lens, n_blocks);
-  } else if (raw_cap <= 32 * 1024) {
-    hipLaunchKernelGGL((lz4_compress_kernel<32 * 1024>), dim3(grid),
-                       dim3(SY_WAVE), 0, stream, d, d_in_off, d_in_len,
-                       o, stride, d_out_lens, n_blocks);
-  } else {
-    hipLaunchKernelGGL((lz4_compress_kernel<64 * 1024>), dim3(grid),
-                       dim3(SY_WAVE), 0, stream, d, d_in_off, d_in_len,
-                       o, stride, d_out_lens, n_blocks);
-  }
-  return sy_check(hipGetLastError());
+  return compress_blocks<SerialMatcher>(d_data, d_in_off, d_in_len, d_out,
+                                        stride, d_out_lens, n_blocks,
+                                        raw_cap, stream);
+}
+
+SY_EXPORT int sy_lz4_compress_blocks_gpu2(
+    const void* d_data, const uint64_t* d_in_off, const uint32_t* d_in_len,
+    void* d_out, uint64_t stride, uint32_t* d_out_lens, uint32_t n_blocks,
+    uint32_t raw_cap, hipStream_t stream) {
+  return compress_blocks<ScreenMatcher>(d_data, d_in_off, d_in_len, d_out,
+                                        stride, d_out_lens, n_blocks,
+                                        raw_cap, stream);
 }

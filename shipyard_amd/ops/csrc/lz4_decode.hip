@@ -25,12 +25,19 @@
 //   resident blocks/CU: +23-75% measured across geometries
 //   (8 KiB synthetic 111 -> 163 GB/s; real text 8 KiB 88 -> 129).
 //
-// Geometry: one wave (64 lanes) per block; LDS = 64 KiB decoded output
-// + 66 KiB staged input (compressed blocks may slightly exceed raw size
-// for incompressible data) -> one workgroup per CU, 256 blocks in
-// flight chip-wide.  Throughput comes from block parallelism; the
-// framework's SYSHARD format stores incompressible blocks raw
-// ("stored"), which bypass this kernel entirely via device memcpy.
+// Geometry (default, v4): one wave (64 lanes) per block, parsing the
+// compressed stream straight from global memory; LDS = RAWCAP bytes of
+// decoded output only.  RAWCAP is the smallest compiled rung
+// (4/8/16/32/64 KiB) that holds the caller's raw_cap; SYSHARD defaults
+// to 8 KiB blocks, so the 8 KiB rung is the one that normally runs
+// (about 9 workgroups per CU, table below).  Throughput comes from
+// block parallelism; the framework's SYSHARD format stores
+// incompressible blocks raw ("stored"), which bypass this kernel
+// entirely via device memcpy.
+// The v3 staged geometry (SY_LZ4_NOSTAGE=0, the SY_LZ4_SKIP probes and
+// the producer/consumer kernel) adds RAWCAP + 1 KiB of LDS for the
+// staged input (compressed blocks may slightly exceed raw size for
+// incompressible data): at 64 KiB that is one workgroup per CU.
 //
 // Match copies use the doubling schedule: round r copies
 // n = min(remaining, done+offset) bytes at read stride -(done+offset)
@@ -38,7 +45,6 @@
 // preserved and every read lands in a completed round.
 
 #include "common.h"
-#include <cstdlib>
 
 namespace {
 
@@ -63,12 +69,63 @@ enum : uint32_t {
 // s_waitcnt immediate: lgkmcnt(0) only (vmcnt/expcnt unconstrained)
 constexpr int kWaitLgkm0 = 0xC07F;
 
+// ---- leaves shared by the single-wave and producer/consumer kernels ----
 
+// Length extension: add 255-run bytes to `len` until one is < 255.
+// Sets `st` to SY_LZ4_ERR_TRUNC when the stream ends first.
+__device__ __forceinline__ void read_len_ext(const uint8_t* src,
+                                             uint32_t& pos, uint32_t slen,
+                                             uint32_t& len, uint32_t& st) {
+  uint8_t b;
+  do {
+    if (pos >= slen) { st = SY_LZ4_ERR_TRUNC; break; }
+    b = src[pos++];
+    len += b;
+  } while (b == 255);
+}
+
+// Longest stream a staged kernel accepts in an sbuf of `src_buf` bytes.
+// -48: staging copies the 16B-aligned enclosing region (up to +15
+// head, +15 tail rounding) — keep the last sbuf slot unwritten
+__device__ __forceinline__ constexpr uint32_t stage_max_slen(int src_buf) {
+  return (uint32_t)src_buf - 48;
+}
+
+// Stage a compressed block into LDS, coalesced 16 B per thread over NT
+// threads.  Copies the 16B-aligned enclosing region so loads stay
+// aligned; returns `srcoff`, where the stream starts inside sbuf.  The
+// caller orders the LDS writes before its first parse read.
+template <int NT>
+__device__ __forceinline__ uint32_t stage_in(uint8_t* sbuf,
+                                             const uint8_t* comp,
+                                             uint64_t abase, uint32_t slen,
+                                             int tid) {
+  const uint64_t astart = abase & ~15ull;
+  const uint32_t srcoff = (uint32_t)(abase - astart);
+  const uint32_t stage_bytes = srcoff + slen;
+  const uint4* g4 = reinterpret_cast<const uint4*>(comp + astart);
+  uint4* s4 = reinterpret_cast<uint4*>(sbuf);
+  const uint32_t n16 = (stage_bytes + 15) >> 4;
+  for (uint32_t i = tid; i < n16; i += NT) s4[i] = g4[i];
+  return srcoff;
+}
+
+// Stream a decoded block LDS -> HBM, coalesced 16 B per thread over NT
+// threads, byte tail last.  `g` is 16B-aligned (out_off contract).
+template <int NT>
+__device__ __forceinline__ void stream_out(uint8_t* g, const uint8_t* dst,
+                                           uint32_t rawlen, int tid) {
+  const uint32_t n16 = rawlen >> 4;
+  const uint4* s4 = reinterpret_cast<const uint4*>(dst);
+  uint4* g4 = reinterpret_cast<uint4*>(g);
+  for (uint32_t i = tid; i < n16; i += NT) g4[i] = s4[i];
+  for (uint32_t i = (n16 << 4) + tid; i < rawlen; i += NT) g[i] = dst[i];
+}
 
 // PROBE: 0 = real decode; 1 = skip literal copies; 2 = skip match
 // copies (both produce WRONG output — perf attribution only, selected
 // via SY_LZ4_SKIP for experiments).
-// STAGE: 1 = stage the compressed block into LDS (default); 0 = parse
+// STAGE: 1 = stage the compressed block into LDS (v3); 0 = parse
 // straight from global memory (the stream is read once, sequentially,
 // so its lines stay hot in the wave's L1) — the ~9 KiB LDS saved per
 // WG roughly doubles resident blocks/CU, and occupancy is the
@@ -91,37 +148,25 @@ __global__ __launch_bounds__(SY_WAVE) void lz4_decode_kernel(
     const uint32_t rawlen = out_len[blk];
     uint32_t st = SY_LZ4_OK;
 
-    // -48: staging copies the 16B-aligned enclosing region (up to +15
-    // head, +15 tail rounding) — keep the last sbuf slot unwritten
-    if ((STAGE && slen > (uint32_t)kSrcBuf - 48) ||
+    if ((STAGE && slen > stage_max_slen(kSrcBuf)) ||
         rawlen > (uint32_t)RAWCAP) {
       if (lane == 0) status[blk] = SY_LZ4_ERR_TOOBIG;
       continue;
     }
 
-    // ---- stage compressed block into LDS (coalesced 16 B/lane) ----
-    // Copy the 16B-aligned enclosing region so loads stay aligned;
-    // the stream starts at `srcoff` inside sbuf.
     {
-      if (STAGE) {
-        const uint64_t astart = abase & ~15ull;
-        const uint32_t srcoff = (uint32_t)(abase - astart);
-        const uint32_t stage_bytes = srcoff + slen;
-        const uint4* g4 = reinterpret_cast<const uint4*>(comp + astart);
-        uint4* s4 = reinterpret_cast<uint4*>(sbuf);
-        const uint32_t n16 = (stage_bytes + 15) >> 4;
-        for (uint32_t i = lane; i < n16; i += SY_WAVE) s4[i] = g4[i];
-        // all lanes' vm loads -> lds writes must land before parsing
-        __builtin_amdgcn_s_waitcnt(0);
-      }
-      // parse below uses src = sbuf + srcoff.  NOTE (measured): a
+      // STAGE: parse from the LDS copy (src = sbuf + srcoff), else
+      // straight from global.  NOTE (measured): a
       // 16 B register-window fetch for header bytes is 45% SLOWER than
       // these per-byte LDS reads — at 9+ waves/CU the read latency is
       // TLP-hidden and the window's extraction VALU + refill join the
       // serial chain instead.
-      const uint8_t* src = STAGE
-          ? sbuf + (uint32_t)(abase - (abase & ~15ull))
-          : comp + abase;
+      const uint8_t* src = comp + abase;
+      if (STAGE) {
+        src = sbuf + stage_in<SY_WAVE>(sbuf, comp, abase, slen, lane);
+        // all lanes' vm loads -> lds writes must land before parsing
+        __builtin_amdgcn_s_waitcnt(0);
+      }
 
       // Uniform parse state (identical in every lane; LDS byte reads
       // of the same address broadcast).
@@ -135,12 +180,7 @@ __global__ __launch_bounds__(SY_WAVE) void lz4_decode_kernel(
         const uint32_t token = src[pos++];
         uint32_t litlen = token >> 4;
         if (litlen == 15) {
-          uint8_t b;
-          do {
-            if (pos >= slen) { st = SY_LZ4_ERR_TRUNC; break; }
-            b = src[pos++];
-            litlen += b;
-          } while (b == 255);
+          read_len_ext(src, pos, slen, litlen, st);
           if (st != SY_LZ4_OK) break;
         }
         if (dpos + litlen > rawlen || pos + litlen > slen) {
@@ -177,12 +217,7 @@ __global__ __launch_bounds__(SY_WAVE) void lz4_decode_kernel(
         pos += 2;
         uint32_t mlen = (token & 0xFu) + 4;
         if ((token & 0xFu) == 15) {
-          uint8_t b;
-          do {
-            if (pos >= slen) { st = SY_LZ4_ERR_TRUNC; break; }
-            b = src[pos++];
-            mlen += b;
-          } while (b == 255);
+          read_len_ext(src, pos, slen, mlen, st);
           if (st != SY_LZ4_OK) break;
         }
         if (offset == 0 || offset > dpos) { st = SY_LZ4_ERR_OFFSET; break; }
@@ -230,14 +265,7 @@ __global__ __launch_bounds__(SY_WAVE) void lz4_decode_kernel(
     if (lane == 0) status[blk] = st;
     if (st == SY_LZ4_OK) {
       __builtin_amdgcn_s_waitcnt(0);
-      // ---- stream LDS -> HBM, coalesced 16 B per lane ----
-      uint8_t* g = out + out_off[blk];
-      const uint32_t n16 = rawlen >> 4;
-      const uint4* s4 = reinterpret_cast<const uint4*>(dst);
-      uint4* g4 = reinterpret_cast<uint4*>(g);  // out_off 16B-aligned
-      for (uint32_t i = lane; i < n16; i += SY_WAVE) g4[i] = s4[i];
-      for (uint32_t i = (n16 << 4) + lane; i < rawlen; i += SY_WAVE)
-        g[i] = dst[i];
+      stream_out<SY_WAVE>(out + out_off[blk], dst, rawlen, lane);
     }
     __builtin_amdgcn_s_waitcnt(0);
   }
@@ -251,110 +279,53 @@ SY_EXPORT int sy_lz4_decode_blocks(const void* d_comp, const uint64_t* d_in_off,
                                    const uint32_t* d_out_len,
                                    uint32_t* d_status, uint32_t n_blocks,
                                    uint32_t raw_cap, hipStream_t stream) {
+  // nothing to decode: success without a launch, whatever raw_cap is
   if (n_blocks == 0) return 0;
-    // Grid cap (SY_LZ4_GRID overrides).  DVFS-warmed sweep on real
+  // Grid cap (SY_LZ4_GRID overrides; 0 or unset = default).
+  // DVFS-warmed sweep on real
   // content at 4 KiB blocks: cap 2048 -> 47 GB/s, 4096 -> 74,
   // 6144 -> 82, 8192 -> 90.5 (and 8 KiB blocks scale the same) —
   // monotone in resident+queued workgroups (8192 -> 197, 16384 -> 216,
   // 32768 -> 229 GB/s synthetic 4 KiB) — hardware dispatch of queued
   // workgroups beats grid-striding; effectively uncapped by default.
-  static uint32_t grid_cap = 0;
-  if (grid_cap == 0) {
-    const char* e = getenv("SY_LZ4_GRID");
-    grid_cap = e ? (uint32_t)atoi(e) : (1u << 22);
-    if (grid_cap == 0) grid_cap = 1u << 22;
-  }
-  uint32_t grid = n_blocks < grid_cap ? n_blocks : grid_cap;
-  const uint8_t* c = static_cast<const uint8_t*>(d_comp);
-  uint8_t* o = static_cast<uint8_t*>(d_out);
-  // perf-attribution probes (WRONG OUTPUT; experiments only)
-  static int probe = -1;
-  if (probe < 0) {
-    const char* e = getenv("SY_LZ4_SKIP");
-    probe = e ? atoi(e) : 0;
-  }
-  if (probe == 1 && raw_cap <= 8 * 1024) {
-    hipLaunchKernelGGL((lz4_decode_kernel<8 * 1024, 1>), dim3(grid),
-                       dim3(SY_WAVE), 0, stream, c, d_in_off, d_in_len, o,
-                       d_out_off, d_out_len, d_status, n_blocks);
-    return sy_check(hipGetLastError());
-  }
-  if (probe == 2 && raw_cap <= 8 * 1024) {
-    hipLaunchKernelGGL((lz4_decode_kernel<8 * 1024, 2>), dim3(grid),
-                       dim3(SY_WAVE), 0, stream, c, d_in_off, d_in_len, o,
-                       d_out_off, d_out_len, d_status, n_blocks);
-    return sy_check(hipGetLastError());
-  }
+  static const uint32_t grid_env = (uint32_t)sy_env_atoi("SY_LZ4_GRID", 0);
+  const uint32_t grid_cap = grid_env ? grid_env : 1u << 22;
+  const uint32_t grid = n_blocks < grid_cap ? n_blocks : grid_cap;
   // v4 DEFAULT: parse straight from global memory (no LDS src
   // staging).  The compressed stream is read once sequentially so its
   // lines stay L1-hot, and the ~9-66 KiB LDS saved per WG doubles
   // resident blocks/CU — measured +23-75% across geometries
   // (profiles/data_plane_r02.md).  SY_LZ4_NOSTAGE=0 forces the v3
   // staged path back for A/B.
-  static int nostage = -1;
-  if (nostage < 0) {
-    const char* e = getenv("SY_LZ4_NOSTAGE");
-    nostage = e ? atoi(e) : 1;
-  }
-  if (nostage) {
-    if (raw_cap <= 4 * 1024) {
-      hipLaunchKernelGGL((lz4_decode_kernel<4 * 1024, 0, 0>), dim3(grid),
-                         dim3(SY_WAVE), 0, stream, c, d_in_off, d_in_len,
-                         o, d_out_off, d_out_len, d_status, n_blocks);
-      return sy_check(hipGetLastError());
-    }
-    if (raw_cap <= 8 * 1024) {
-      hipLaunchKernelGGL((lz4_decode_kernel<8 * 1024, 0, 0>), dim3(grid),
-                         dim3(SY_WAVE), 0, stream, c, d_in_off, d_in_len,
-                         o, d_out_off, d_out_len, d_status, n_blocks);
-      return sy_check(hipGetLastError());
-    }
-    if (raw_cap <= 16 * 1024) {
-      hipLaunchKernelGGL((lz4_decode_kernel<16 * 1024, 0, 0>),
-                         dim3(grid), dim3(SY_WAVE), 0, stream, c,
-                         d_in_off, d_in_len, o, d_out_off, d_out_len,
-                         d_status, n_blocks);
-      return sy_check(hipGetLastError());
-    }
-    if (raw_cap <= 32 * 1024) {
-      hipLaunchKernelGGL((lz4_decode_kernel<32 * 1024, 0, 0>),
-                         dim3(grid), dim3(SY_WAVE), 0, stream, c,
-                         d_in_off, d_in_len, o, d_out_off, d_out_len,
-                         d_status, n_blocks);
-      return sy_check(hipGetLastError());
-    }
-    if (raw_cap <= 64 * 1024) {
-      hipLaunchKernelGGL((lz4_decode_kernel<64 * 1024, 0, 0>),
-                         dim3(grid), dim3(SY_WAVE), 0, stream, c,
-                         d_in_off, d_in_len, o, d_out_off, d_out_len,
-                         d_status, n_blocks);
-      return sy_check(hipGetLastError());
-    }
-  }
-  if (raw_cap <= 4 * 1024) {
-    hipLaunchKernelGGL((lz4_decode_kernel<4 * 1024>), dim3(grid),
-                       dim3(SY_WAVE), 0, stream, c, d_in_off, d_in_len, o,
-                       d_out_off, d_out_len, d_status, n_blocks);
-  } else if (raw_cap <= 8 * 1024) {
-    hipLaunchKernelGGL((lz4_decode_kernel<8 * 1024>), dim3(grid),
-                       dim3(SY_WAVE), 0, stream, c, d_in_off, d_in_len, o,
-                       d_out_off, d_out_len, d_status, n_blocks);
-  } else if (raw_cap <= 16 * 1024) {
-    hipLaunchKernelGGL((lz4_decode_kernel<16 * 1024>), dim3(grid),
-                       dim3(SY_WAVE), 0, stream, c, d_in_off, d_in_len, o,
-                       d_out_off, d_out_len, d_status, n_blocks);
-  } else if (raw_cap <= 32 * 1024) {
-    hipLaunchKernelGGL((lz4_decode_kernel<32 * 1024>), dim3(grid),
-                       dim3(SY_WAVE), 0, stream, c, d_in_off, d_in_len, o,
-                       d_out_off, d_out_len, d_status, n_blocks);
-  } else if (raw_cap <= 64 * 1024) {
-    hipLaunchKernelGGL((lz4_decode_kernel<64 * 1024>), dim3(grid),
-                       dim3(SY_WAVE), 0, stream, c, d_in_off, d_in_len, o,
-                       d_out_off, d_out_len, d_status, n_blocks);
-  } else {
-    return -22;
-  }
-  return sy_check(hipGetLastError());
+  static const bool stage = sy_env_atoi("SY_LZ4_NOSTAGE", 1) == 0;
+  // Perf-attribution probes (WRONG OUTPUT; experiments only):
+  // SY_LZ4_SKIP=1|2 takes effect only for raw_cap <= 8 KiB, where it
+  // runs the staged 8 KiB instantiation whatever SY_LZ4_NOSTAGE says.
+  // Any other value or a larger raw_cap is the normal path.
+  static const int probe_env = sy_env_atoi("SY_LZ4_SKIP", 0);
+  const int probe = raw_cap <= 8 * 1024 ? probe_env : 0;
+  const bool probing = probe == 1 || probe == 2;
+
+  auto launch = [&](auto* kernel) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(SY_WAVE), 0, stream,
+                       static_cast<const uint8_t*>(d_comp), d_in_off,
+                       d_in_len, static_cast<uint8_t*>(d_out), d_out_off,
+                       d_out_len, d_status, n_blocks);
+    return sy_check(hipGetLastError());
+  };
+  // raw_cap > 64 KiB is -22 under every environment setting.  A probe
+  // asks for exactly 8 KiB, which lands on the 8 KiB rung.
+  return sy_dispatch_rung<4 * 1024, 8 * 1024, 16 * 1024, 32 * 1024,
+                          64 * 1024>(
+      probing ? 8 * 1024 : raw_cap, [&](auto cap) {
+        constexpr int CAP = decltype(cap)::value;
+        if constexpr (CAP == 8 * 1024) {
+          if (probe == 1) return launch(lz4_decode_kernel<CAP, 1, 1>);
+          if (probe == 2) return launch(lz4_decode_kernel<CAP, 2, 1>);
+        }
+        return stage ? launch(lz4_decode_kernel<CAP, 0, 1>)
+                     : launch(lz4_decode_kernel<CAP, 0, 0>);
+      });
 }
 
 namespace {
@@ -404,22 +375,15 @@ __global__ __launch_bounds__(2 * SY_WAVE) void lz4_decode_pc_kernel(
     const uint32_t slen = in_len[blk];
     const uint32_t rawlen = out_len[blk];
 
-    if (slen > (uint32_t)kSrcBuf - 48 || rawlen > (uint32_t)RAWCAP) {
+    if (slen > stage_max_slen(kSrcBuf) || rawlen > (uint32_t)RAWCAP) {
       if (tid == 0) status[blk] = SY_LZ4_ERR_TOOBIG;
       __syncthreads();
       continue;
     }
 
-    // ---- stage compressed block into LDS (both waves, 16 B/lane) ----
-    const uint64_t astart = abase & ~15ull;
-    const uint32_t srcoff = (uint32_t)(abase - astart);
-    const uint32_t stage_bytes = srcoff + slen;
-    {
-      const uint4* g4 = reinterpret_cast<const uint4*>(comp + astart);
-      uint4* s4 = reinterpret_cast<uint4*>(sbuf);
-      const uint32_t n16 = (stage_bytes + 15) >> 4;
-      for (uint32_t i = tid; i < n16; i += 2 * SY_WAVE) s4[i] = g4[i];
-    }
+    // ---- stage compressed block into LDS (both waves) ----
+    const uint32_t srcoff =
+        stage_in<2 * SY_WAVE>(sbuf, comp, abase, slen, tid);
     if (tid == 0) {
       ctl[0] = 0; ctl[1] = 0; ctl[2] = SY_LZ4_OK; ctl[3] = 0;
     }
@@ -440,12 +404,7 @@ __global__ __launch_bounds__(2 * SY_WAVE) void lz4_decode_pc_kernel(
         const uint32_t token = src[pos++];
         uint32_t litlen = token >> 4;
         if (litlen == 15) {
-          uint8_t b;
-          do {
-            if (pos >= slen) { st = SY_LZ4_ERR_TRUNC; break; }
-            b = src[pos++];
-            litlen += b;
-          } while (b == 255);
+          read_len_ext(src, pos, slen, litlen, st);
           if (st != SY_LZ4_OK) break;
         }
         if (dtotal + litlen > rawlen || pos + litlen > slen) {
@@ -462,12 +421,7 @@ __global__ __launch_bounds__(2 * SY_WAVE) void lz4_decode_pc_kernel(
           pos += 2;
           mlen = (token & 0xFu) + 4;
           if ((token & 0xFu) == 15) {
-            uint8_t b;
-            do {
-              if (pos >= slen) { st = SY_LZ4_ERR_TRUNC; break; }
-              b = src[pos++];
-              mlen += b;
-            } while (b == 255);
+            read_len_ext(src, pos, slen, mlen, st);
             if (st != SY_LZ4_OK) break;
           }
           if (offset == 0 || offset > dtotal) {
@@ -585,14 +539,8 @@ __global__ __launch_bounds__(2 * SY_WAVE) void lz4_decode_pc_kernel(
     const uint32_t st = ctl[2];
     if (tid == 0) status[blk] = st;
     if (st == SY_LZ4_OK) {
-      // ---- stream LDS -> HBM (both waves) ----
-      uint8_t* g = out + out_off[blk];
-      const uint32_t n16 = rawlen >> 4;
-      const uint4* s4 = reinterpret_cast<const uint4*>(dst);
-      uint4* g4 = reinterpret_cast<uint4*>(g);
-      for (uint32_t i = tid; i < n16; i += 2 * SY_WAVE) g4[i] = s4[i];
-      for (uint32_t i = (n16 << 4) + tid; i < rawlen; i += 2 * SY_WAVE)
-        g[i] = dst[i];
+      // both waves
+      stream_out<2 * SY_WAVE>(out + out_off[blk], dst, rawlen, tid);
     }
     __syncthreads();
   }
@@ -605,24 +553,19 @@ SY_EXPORT int sy_lz4_decode_blocks_pc(
     void* d_out, const uint64_t* d_out_off, const uint32_t* d_out_len,
     uint32_t* d_status, uint32_t n_blocks, uint32_t raw_cap,
     hipStream_t stream) {
+  // nothing to decode: success without a launch, whatever raw_cap is
   if (n_blocks == 0) return 0;
-  uint32_t grid = n_blocks < 4096u ? n_blocks : 4096u;
-  const uint8_t* c = static_cast<const uint8_t*>(d_comp);
-  uint8_t* o = static_cast<uint8_t*>(d_out);
-  if (raw_cap <= 8 * 1024) {
-    hipLaunchKernelGGL((lz4_decode_pc_kernel<8 * 1024>), dim3(grid),
-                       dim3(2 * SY_WAVE), 0, stream, c, d_in_off, d_in_len,
-                       o, d_out_off, d_out_len, d_status, n_blocks);
-  } else if (raw_cap <= 16 * 1024) {
-    hipLaunchKernelGGL((lz4_decode_pc_kernel<16 * 1024>), dim3(grid),
-                       dim3(2 * SY_WAVE), 0, stream, c, d_in_off, d_in_len,
-                       o, d_out_off, d_out_len, d_status, n_blocks);
-  } else if (raw_cap <= 64 * 1024) {
-    hipLaunchKernelGGL((lz4_decode_pc_kernel<64 * 1024>), dim3(grid),
-                       dim3(2 * SY_WAVE), 0, stream, c, d_in_off, d_in_len,
-                       o, d_out_off, d_out_len, d_status, n_blocks);
-  } else {
-    return -22;
-  }
-  return sy_check(hipGetLastError());
+  // fixed grid cap; SY_LZ4_GRID and the other knobs do not apply here
+  const uint32_t grid = n_blocks < 4096u ? n_blocks : 4096u;
+  // No 4 KiB or 32 KiB rung: those raw_caps run at 8 and 64 KiB.
+  // raw_cap > 64 KiB is -22.
+  return sy_dispatch_rung<8 * 1024, 16 * 1024, 64 * 1024>(
+      raw_cap, [&](auto cap) {
+        hipLaunchKernelGGL(lz4_decode_pc_kernel<decltype(cap)::value>,
+                           dim3(grid), dim3(2 * SY_WAVE), 0, stream,
+                           static_cast<const uint8_t*>(d_comp), d_in_off,
+                           d_in_len, static_cast<uint8_t*>(d_out),
+                           d_out_off, d_out_len, d_status, n_blocks);
+        return sy_check(hipGetLastError());
+      });
 }

@@ -257,22 +257,64 @@ class TestLz4DecodeEdges:
     def test_staged_path_in_child_process(self):
         """SY_LZ4_NOSTAGE is read once per process, so the staged v3
         kernels (LDS-staged source, 16 B-aligned enclosing copy of an
-        unaligned stream) run in one fresh child interpreter."""
+        unaligned stream) run in one fresh child interpreter: every rung
+        of the staged ladder, then the -22 rejection above the top rung,
+        which must hold under this setting too."""
         here = os.path.dirname(os.path.abspath(__file__))
         root = os.path.dirname(here)
         code = (
             "import sys\n"
             "sys.path[:0] = [%r, %r]\n"
             "import ops_edge_corpus as c\n"
+            "c.check_guarded_fuzz(4096, False, 40)\n"
             "c.check_guarded_fuzz(8192, False, 41)\n"
+            "c.check_guarded_fuzz(16384, False, 43)\n"
+            "c.check_guarded_fuzz(32768, False, 44)\n"
             "c.check_guarded_fuzz(65536, False, 42)\n"
+            "try:\n"
+            "    c.guarded_decode([c.accepted_lz4_case()[1]], [5], 65537,\n"
+            "                     False, stride=c.slot_stride(65536))\n"
+            "except RuntimeError as e:\n"
+            "    assert '-22' in str(e), e\n"
+            "else:\n"
+            "    raise AssertionError('raw_cap 65537 was accepted')\n"
             "print('OK')\n" % (here, root))
+        # five geometries + interpreter and torch start-up
         res = subprocess.run(
             [sys.executable, "-c", code],
-            env={**os.environ, "SY_LZ4_NOSTAGE": "0"}, timeout=120,
+            env={**os.environ, "SY_LZ4_NOSTAGE": "0"}, timeout=300,
             capture_output=True, text=True)
         assert res.returncode == 0, res.stdout + res.stderr
         assert res.stdout.strip().splitlines()[-1] == "OK"
+
+    @pytest.mark.parametrize("pc", [False, True])
+    @pytest.mark.parametrize("raw_cap", [4097, 8193, 16385, 32769])
+    def test_off_rung_routing(self, raw_cap, pc):
+        """A raw_cap one past a rung runs the next compiled rung: a block
+        of exactly that rung's size decodes, and in the same launch a
+        block one byte longer is TOOBIG with its slot untouched.  An
+        instantiation one rung too small would report the first block
+        TOOBIG, one too large would accept the second."""
+        rung = _pc_effective_cap(raw_cap) if pc else \
+            next(c for c in _RAW_CAPS if c >= raw_cap)
+        import random
+
+        raw = corpus.mixed_content(random.Random(raw_cap + int(pc)), rung)
+        stream = lz4py.compress_block(raw)
+        status, got, stride = corpus.guarded_decode(
+            [stream, stream], [rung, rung + 1], raw_cap, pc,
+            stride=corpus.slot_stride(rung))
+        assert status == [corpus.OK, corpus.ERR_TOOBIG]
+        corpus.check_slots(got, stride, [raw, b""])
+
+    @pytest.mark.parametrize("pc", [False, True])
+    def test_raw_cap_above_top_rung_is_rejected(self, pc):
+        """raw_cap = 65537 has no rung: the host wrapper returns -22
+        before any launch."""
+        name, stream, out_len, raw = corpus.accepted_lz4_case()
+        with pytest.raises(RuntimeError, match="-22"):
+            corpus.guarded_decode([stream], [out_len], 65537, pc,
+                                  stride=corpus.slot_stride(65536))
 
 
 # --------------------------------------------------------- GPU compressors
@@ -340,6 +382,16 @@ class TestGpuCompressorEdges:
                                raws)
         # bound taken from TestScreenCompressor.test_roundtrip_and_ratio
         assert comp_v2 <= comp_v1 * 1.25 + 1024, (comp_v1, comp_v2)
+
+    @pytest.mark.parametrize("screen", [False, True])
+    def test_block_raw_above_top_rung_is_rejected(self, screen):
+        """block_raw = 64 KiB + 4 KiB has no rung in either matcher
+        family: the host wrapper returns -22 before any launch."""
+        from shipyard_amd import ops
+
+        data = _cuda(_seeded(7, 65536 + 4096))
+        with pytest.raises(RuntimeError, match="-22"):
+            ops.lz4_compress_blocks_gpu(data, 65536 + 4096, screen=screen)
 
     @pytest.mark.parametrize("screen", [False, True])
     def test_encoding_edges(self, screen):
