@@ -15,7 +15,11 @@ Layout (little-endian):
                         with bit1, 0 without
                         bit2: FILTER_DELTA, blocks hold element deltas
                         bits 16..23: delta element size D — 2, 4 or 8
-                        with bit2, 0 without; other bits ignored)
+                        with bit2, 0 without
+                        bit3: FILTER_BITSHUFFLE, blocks are bit-shuffled
+                        bits 24..31: bitshuffle element size B — 2, 4 or
+                        8 with bit3, 0 without; other bits ignored;
+                        bit1 and bit3 exclude each other)
   u32 block_raw        (max raw bytes per block; 8 KiB default)
   u64 raw_size
   u32 n_blocks
@@ -58,13 +62,42 @@ shard: data that is not monotone (uniform token ids) gets WORSE under
 delta, because differences of independent values are noisier than the
 values.
 
+FILTER_BITSHUFFLE (float fields and weights, narrow-range integers:
+the filter HDF5 bitshuffle and Blosc BITSHUFFLE put in front of their
+codecs) transposes every block bit by bit, so that a bit position that
+is nearly constant over the elements (a sign, high exponent bits, the
+unused top bits of a small delta) becomes a run of equal bytes even
+where it shares its byte with noisy bits.  For a block of raw_len
+bytes, n_el = raw_len // B, n8 = n_el // 8 * 8, L = n8 // 8 and
+body = n8 * B; elements are little-endian, and bit p of an element
+(0 <= p < 8*B) is bit p % 8, counted LSB first, of its byte p // 8:
+
+  plane p occupies filtered[p*L : (p+1)*L]              0 <= p < 8*B
+  bit r (LSB first) of filtered[p*L + m] = bit p of element 8*m + r
+  filtered[body:] = raw[body:]
+
+The verbatim tail holds the n_el % 8 leftover elements and the
+raw_len % B leftover bytes (a full block of a 4096-multiple block size
+has none).  The per-block crc32c is that of the ORIGINAL bytes.
+Writers apply delta, then bitshuffle, then shuffle, then LZ4 or store;
+bitshuffle composes with delta, but bitshuffle and the byte shuffle
+exclude each other (a byte shuffle of bit planes is meaningless):
+asking for both, at a writer, in an index or in a header's flags, is a
+ValueError.  The filter is opt-in per shard: skewed token ids pack
+WORSE bit-shuffled than byte-shuffled (docs/35-gpu-data-plane.md).
+
 Adding a filter: add a row to ``FILTERS`` at its place in the writer
 order (flag bit, element-size bits, whether the device op may run in
 place), a numpy body transform for ``_filter_blocks`` as its reference,
 an ``ops`` binding with the arguments of ``ops.byte_shuffle``, and the
 kernel behind it; then add the row's keyword to the writers' signatures
 and to ``ShardIndex``.  Flags, header parsing, validation and the CPU
-and device chains in both directions all follow from the row.
+and device chains in both directions all follow from the row.  A filter
+that transforms its elements in groups passes the group size to
+``_filter_blocks`` as ``granule`` (bitshuffle: 8 elements; what does not
+fill a group stays verbatim), and one that makes no sense together with
+another gets a pair in ``EXCLUSIVE_FILTERS``, which every writer,
+``validate_index`` and the header parser check.
 """
 from __future__ import annotations
 
@@ -98,12 +131,13 @@ FILTER_ELEM_SIZES = (2, 4, 8)
 
 
 def _filter_blocks(data, block_raw: int, elem_size: int, inverse: bool,
-                   body_fn) -> bytes:
+                   body_fn, granule: int = 1) -> bytes:
     """Walk ``data`` as ``block_raw`` blocks (the last may be short):
-    ``body_fn(x, elem_size, inverse)`` transforms the whole elements of
-    a batch of equally long blocks, an ``(n_blk, body)`` uint8 view,
-    and the ``len % elem_size`` leftover of every block is copied
-    verbatim.  One call for all full blocks, one for the ragged one."""
+    ``body_fn(x, elem_size, inverse)`` transforms the whole groups of
+    ``granule`` elements of a batch of equally long blocks, an
+    ``(n_blk, body)`` uint8 view, and the ``len % (granule *
+    elem_size)`` leftover of every block is copied verbatim.  One call
+    for all full blocks, one for the ragged one."""
     import numpy as np
 
     if elem_size not in FILTER_ELEM_SIZES:
@@ -117,7 +151,7 @@ def _filter_blocks(data, block_raw: int, elem_size: int, inverse: bool,
                                (n_full * block_raw, 1, tail_len)):
         if not n_blk or not blk_len:
             continue
-        body = blk_len // elem_size * elem_size
+        body = blk_len // (granule * elem_size) * (granule * elem_size)
         s = src[lo:lo + n_blk * blk_len].reshape(n_blk, blk_len)
         d = out[lo:lo + n_blk * blk_len].reshape(n_blk, blk_len)
         if body:
@@ -143,6 +177,21 @@ def _delta_body(x, E: int, inverse: bool):
         y = x.copy()
         y[:, 1:] -= x[:, :-1]
     return y.view(np.uint8)
+
+
+def _bitshuffle_body(x, E: int, inverse: bool):
+    import numpy as np
+
+    n_blk, body = x.shape
+    n8 = body // E
+    if inverse:
+        bits = np.unpackbits(x.reshape(n_blk, 8 * E, n8 // 8), axis=2,
+                             bitorder="little")
+    else:
+        bits = np.unpackbits(x.reshape(n_blk, n8, E), axis=2,
+                             bitorder="little")
+    return np.packbits(bits.transpose(0, 2, 1), axis=2,
+                       bitorder="little").reshape(n_blk, body)
 
 
 def shuffle_blocks_numpy(data, block_raw: int, elem_size: int,
@@ -171,6 +220,21 @@ def delta_blocks_numpy(data, block_raw: int, elem_size: int,
     return _filter_blocks(data, block_raw, elem_size, inverse, _delta_body)
 
 
+def bitshuffle_blocks_numpy(data, block_raw: int, elem_size: int,
+                            inverse: bool = False) -> bytes:
+    """Reference bit-shuffle of ``data`` laid out as ``block_raw``
+    blocks (the last may be short): per block, the whole groups of 8
+    ``elem_size``-byte little-endian elements are bit-transposed, so
+    that plane p holds bit p of every element, 8 consecutive elements
+    per byte, LSB first; what does not fill a group of 8 elements is
+    copied verbatim; ``inverse`` undoes it.  Vectorised: one
+    ``unpackbits`` / transpose / ``packbits`` for all full blocks, one
+    for the ragged block.  The CPU writer, the CPU reader and the tests
+    of the device kernel (ops.bit_shuffle) share it."""
+    return _filter_blocks(data, block_raw, elem_size, inverse,
+                          _bitshuffle_body, granule=8)
+
+
 @dataclass(frozen=True)
 class Filter:
     """One row of FILTERS: everything the format code knows about a
@@ -189,16 +253,31 @@ class Filter:
 FILTERS = (
     Filter("delta_elem", "FILTER_DELTA", 0x4, 16, FILTER_ELEM_SIZES,
            delta_blocks_numpy, "delta_filter", in_place=True),
+    Filter("bitshuffle_elem", "FILTER_BITSHUFFLE", 0x8, 24,
+           FILTER_ELEM_SIZES, bitshuffle_blocks_numpy, "bit_shuffle",
+           in_place=False),
     Filter("shuffle_elem", "FILTER_SHUFFLE", 0x2, 8, FILTER_ELEM_SIZES,
            shuffle_blocks_numpy, "byte_shuffle", in_place=False),
 )
+
+# pairs of filter keywords that may not both be on
+EXCLUSIVE_FILTERS = (("bitshuffle_elem", "shuffle_elem"),)
+
+
+def _check_exclusive(what: str, elems: dict) -> None:
+    for a, b in EXCLUSIVE_FILTERS:
+        if elems.get(a, 0) and elems.get(b, 0):
+            raise ValueError(
+                f"{what}: {a}={elems[a]} and {b}={elems[b]} exclude "
+                "each other, at most one of them may be non-zero")
 
 
 def _filter_elems(what: str, given) -> dict:
     """``{keyword: element size}`` of every filter (0: off), in writer
     order, from a mapping that holds them under their keyword names (a
     writer's ``locals()``, a ShardIndex's ``vars()``).  ValueError in
-    ``what``'s name for a size the filter does not take."""
+    ``what``'s name for a size the filter does not take, or for two
+    filters on that exclude each other."""
     elems = {}
     for f in FILTERS:
         elem = given.get(f.kwarg, 0)
@@ -207,12 +286,14 @@ def _filter_elems(what: str, given) -> dict:
                 f"{what}: {f.kwarg}={elem} must be 0 (no filter) "
                 f"or one of {f.sizes}")
         elems[f.kwarg] = int(elem)
+    _check_exclusive(what, elems)
     return elems
 
 
 def _active(elems: dict) -> list:
-    """(filter, element size) of the filters that are on, writer order."""
-    return [(f, elems[f.kwarg]) for f in FILTERS if elems[f.kwarg]]
+    """(filter, element size) of the filters that are on, writer order;
+    a keyword that ``elems`` lacks means that its filter is off."""
+    return [(f, elems[f.kwarg]) for f in FILTERS if elems.get(f.kwarg, 0)]
 
 
 def filter_flags(elems: dict) -> int:
@@ -227,7 +308,8 @@ def filter_elems_from_flags(flags: int) -> dict:
     """Element size of every filter named by a header's flags word; 0
     where the filter's bit is clear (its element-size bits are then
     ignored like every other unknown bit).  ValueError when a filter is
-    on with an element size it does not take."""
+    on with an element size it does not take, or when two filters are
+    on that exclude each other."""
     elems = {}
     for f in FILTERS:
         elem = (flags >> f.shift) & 0xFF if flags & f.flag else 0
@@ -236,6 +318,7 @@ def filter_elems_from_flags(flags: int) -> dict:
                 f"SYSHARD flags {flags:#x}: {f.flag_name} with element "
                 f"size {elem}, must be one of {f.sizes}")
         elems[f.kwarg] = elem
+    _check_exclusive(f"SYSHARD flags {flags:#x}", elems)
     return elems
 
 
@@ -314,11 +397,13 @@ class ShardIndex:
     decode without per-block python; `.blocks` materializes the
     BlockEntry view lazily for tests/CPU paths.  ``shuffle_elem`` is
     the FILTER_SHUFFLE element size and ``delta_elem`` the FILTER_DELTA
-    one (0: that filter is off)."""
+    one, ``bitshuffle_elem`` the FILTER_BITSHUFFLE one (0: that filter
+    is off)."""
 
     def __init__(self, block_raw: int, raw_size: int, payload_off: int,
                  table=None, blocks: List[BlockEntry] = None, *,
-                 shuffle_elem: int = 0, delta_elem: int = 0):
+                 shuffle_elem: int = 0, delta_elem: int = 0,
+                 bitshuffle_elem: int = 0):
         import numpy as np
 
         self.block_raw = block_raw
@@ -326,6 +411,7 @@ class ShardIndex:
         self.payload_off = payload_off
         self.shuffle_elem = shuffle_elem
         self.delta_elem = delta_elem
+        self.bitshuffle_elem = bitshuffle_elem
         if table is None:
             blocks = blocks or []
             table = np.zeros(len(blocks), dtype=_entry_dt())
@@ -375,7 +461,8 @@ def _compress_span(args):
 
 def pack(data: bytes, block_raw: int = DEFAULT_BLOCK_RAW,
          compress: bool = True, workers: Optional[int] = None,
-         shuffle_elem: int = 0, delta_elem: int = 0) -> bytes:
+         shuffle_elem: int = 0, delta_elem: int = 0,
+         bitshuffle_elem: int = 0) -> bytes:
     """Pack raw bytes into SYSHARD format (CPU writer).
 
     `shuffle_elem` (2, 4 or 8; 0 = off) byte-shuffles every block over
@@ -388,6 +475,12 @@ def pack(data: bytes, block_raw: int = DEFAULT_BLOCK_RAW,
     ahead of the shuffle; meant for monotone data such as offsets,
     sorted ids and timestamps, and opt-in because it makes other data
     compress worse.
+
+    `bitshuffle_elem` (2, 4 or 8; 0 = off) bit-transposes every block
+    over elements of that size (FILTER_BITSHUFFLE), after the delta and
+    instead of the byte shuffle (ValueError with `shuffle_elem` also
+    non-zero); meant for float weights and fields and for delta-coded
+    offsets, and opt-in because skewed token ids compress worse.
 
     `workers`: block compression is embarrassingly parallel (blocks are
     independent LZ4 streams); None = serial, 0 = one per CPU.  The
@@ -461,7 +554,8 @@ def gpu_block_raw_ok(block_raw: int) -> bool:
 
 
 def pack_gpu(data, block_raw: int = DEFAULT_BLOCK_RAW,
-             shuffle_elem: int = 0, delta_elem: int = 0) -> bytes:
+             shuffle_elem: int = 0, delta_elem: int = 0,
+             bitshuffle_elem: int = 0) -> bytes:
     """GPU SYSHARD writer: block compression (ops GPU matcher) +
     per-block CRC32C both run on the MI355X; the host only assembles
     header/table around the copied-back payload.  ``data``: bytes or a
@@ -484,7 +578,13 @@ def pack_gpu(data, block_raw: int = DEFAULT_BLOCK_RAW,
     buffer (a tensor passed in stays untouched), and with both filters
     on ops.byte_shuffle reads that buffer, which is freed as soon as
     the shuffled copy exists.  Output equals
-    ``pack(..., delta_elem=...)`` under the same matcher rule."""
+    ``pack(..., delta_elem=...)`` under the same matcher rule.
+
+    ``bitshuffle_elem`` (2, 4 or 8; 0 = off) applies FILTER_BITSHUFFLE
+    in the byte shuffle's place (ValueError with both non-zero):
+    ops.bit_shuffle writes the bit planes into a new buffer, after the
+    delta when that is on too.  Output equals
+    ``pack(..., bitshuffle_elem=...)`` under the same matcher rule."""
     if not gpu_block_raw_ok(block_raw):
         raise ValueError(
             f"pack_gpu: block_raw={block_raw} must be a multiple of "
@@ -581,7 +681,8 @@ def pack_gpu(data, block_raw: int = DEFAULT_BLOCK_RAW,
 def pack_auto(data: bytes, block_raw: int = DEFAULT_BLOCK_RAW,
               workers: Optional[int] = None,
               gpu_threshold: int = 1 << 20,
-              shuffle_elem: int = 0, delta_elem: int = 0) -> bytes:
+              shuffle_elem: int = 0, delta_elem: int = 0,
+              bitshuffle_elem: int = 0) -> bytes:
     """Author a SYSHARD on the GPU when one is present and the
     payload is large enough to amortize the H2D hop; CPU writer
     otherwise.  Both outputs are valid shards that every reader
@@ -590,8 +691,8 @@ def pack_auto(data: bytes, block_raw: int = DEFAULT_BLOCK_RAW,
     ~equal ratio but not bit-identical — decode-side parity measured
     in profiles/data_plane_r02.md).  Block sizes the GPU writer cannot
     handle (see ``pack_gpu``) always take the CPU writer.
-    ``shuffle_elem`` and ``delta_elem`` go to whichever writer is
-    picked."""
+    ``shuffle_elem``, ``delta_elem`` and ``bitshuffle_elem`` go to
+    whichever writer is picked."""
     elems = _filter_elems("pack_auto", locals())
     if len(data) >= gpu_threshold and gpu_block_raw_ok(block_raw):
         try:
@@ -661,6 +762,8 @@ def validate_index(idx: ShardIndex, payload_len: int,
       block is compressed (stored-only shards may use larger blocks)
     * shuffle_elem is 0, 2, 4 or 8 (ops.byte_shuffle takes no other)
     * delta_elem is 0, 2, 4 or 8 (ops.delta_filter takes no other)
+    * bitshuffle_elem is 0, 2, 4 or 8 (ops.bit_shuffle takes no other),
+      and bitshuffle_elem and shuffle_elem are not both non-zero
 
     O(n_blocks) vectorized numpy; ``unpack_cpu`` stays permissive and
     does not call this."""
@@ -834,9 +937,9 @@ def decode_device(d_comp, idx: ShardIndex, device, verify: bool = True):
     stored-contiguous fast path the payload itself, which is never
     aliased or modified: a filtered shard's output is then a new tensor
     and ``d_comp``'s base must be 16-byte aligned.  Un-delta runs in
-    place on anything but the payload, unshuffle never does, so the
-    peak HBM use on top of the payload is 1x raw for delta alone and 2x
-    raw when shuffle is on."""
+    place on anything but the payload, unshuffle and un-bitshuffle
+    never do, so the peak HBM use on top of the payload is 1x raw for
+    delta alone and 2x raw when shuffle or bitshuffle is on."""
     validate_index(idx, d_comp.numel(), for_gpu=True)
 
     import torch
@@ -882,7 +985,7 @@ def unpack_gpu(buf: bytes, device=None, verify: bool = True):
 
 def pack_file(src: Path, dst: Path, block_raw: int = DEFAULT_BLOCK_RAW,
               compress: bool = True, shuffle_elem: int = 0,
-              delta_elem: int = 0) -> ShardIndex:
+              delta_elem: int = 0, bitshuffle_elem: int = 0) -> ShardIndex:
     data = Path(src).read_bytes()
     packed = pack(data, block_raw=block_raw, compress=compress,
                   **_filter_elems("pack_file", locals()))

@@ -42,11 +42,14 @@ class ObjectStore:
                      pack: bool = False,
                      manifest: bool = False,
                      shuffle_elem: int = 0,
-                     delta_elem: int = 0) -> Path:
+                     delta_elem: int = 0,
+                     bitshuffle_elem: int = 0) -> Path:
         """``shuffle_elem`` (with ``pack``): byte-shuffle filter element
         size for typed numeric payloads; ``delta_elem``: delta filter
         element size for monotone ones (offsets, sorted ids,
-        timestamps).  See shardfmt.pack."""
+        timestamps); ``bitshuffle_elem``: bit-shuffle filter element
+        size for float weights and fields, in the byte shuffle's place.
+        See shardfmt.pack."""
         dst = self._path(remote_path)
         dst.parent.mkdir(parents=True, exist_ok=True)
         if pack:
@@ -56,7 +59,7 @@ class ObjectStore:
             workers = 0 if len(data) > (4 << 20) else None
             dst.write_bytes(shardfmt.pack_auto(
                 data, workers=workers, shuffle_elem=shuffle_elem,
-                delta_elem=delta_elem))
+                delta_elem=delta_elem, bitshuffle_elem=bitshuffle_elem))
         else:
             dst.write_bytes(data)
         if manifest:
@@ -66,13 +69,15 @@ class ObjectStore:
     def upload_file(self, local_path, remote_path: str,
                     pack: bool = False, manifest: bool = False,
                     shuffle_elem: int = 0,
-                    delta_elem: int = 0) -> Path:
+                    delta_elem: int = 0,
+                    bitshuffle_elem: int = 0) -> Path:
         data = Path(local_path).read_bytes() if (pack or manifest) else None
         if pack or manifest:
             return self.upload_bytes(remote_path, data, pack=pack,
                                      manifest=manifest,
                                      shuffle_elem=shuffle_elem,
-                                     delta_elem=delta_elem)
+                                     delta_elem=delta_elem,
+                                     bitshuffle_elem=bitshuffle_elem)
         dst = self._path(remote_path)
         dst.parent.mkdir(parents=True, exist_ok=True)
         shutil.copy2(local_path, dst)

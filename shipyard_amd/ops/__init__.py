@@ -126,6 +126,8 @@ def _load() -> ctypes.CDLL:
     ]
     lib.sy_delta_filter.restype = ctypes.c_int
     lib.sy_delta_filter.argtypes = lib.sy_byte_shuffle.argtypes
+    lib.sy_bit_shuffle.restype = ctypes.c_int
+    lib.sy_bit_shuffle.argtypes = lib.sy_byte_shuffle.argtypes
     lib.sy_lz4_compress_blocks_gpu.restype = ctypes.c_int
     lib.sy_lz4_compress_blocks_gpu.argtypes = [
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
@@ -492,6 +494,28 @@ def delta_filter(src, dst, block_raw: int, elem_size: int,
     One workgroup decodes one block from start to end, so a buffer of a
     few very large blocks uses only a few CUs."""
     _block_filter("delta_filter", "sy_delta_filter", True, src, dst,
+                  block_raw, elem_size, inverse)
+
+
+def bit_shuffle(src, dst, block_raw: int, elem_size: int,
+                inverse: bool = False):
+    """SYSHARD bit-shuffle filter on the device: ``dst`` receives
+    ``src`` with every ``block_raw`` block (the last one may be short)
+    bit-transposed over ``elem_size``-byte little-endian elements —
+    plane p of a block holds bit p of each of its elements, 8
+    consecutive elements per byte, LSB first; what does not fill a
+    group of 8 elements (only in a ragged final block) is copied
+    verbatim.  ``inverse=True`` undoes it.  The byte layout is
+    ``shardfmt.bitshuffle_blocks_numpy``'s.
+
+    ``src``/``dst``: contiguous uint8 CUDA tensors of equal numel whose
+    base pointers are 16-byte aligned and whose byte ranges do not
+    overlap (the filter does not run in place); ``elem_size`` in
+    {2, 4, 8}; ``block_raw`` a positive multiple of 4096 below 2**32.
+    Each violation is a ValueError raised before any launch (and ahead
+    of the device assert, so the rules are testable on hosts without a
+    GPU)."""
+    _block_filter("bit_shuffle", "sy_bit_shuffle", False, src, dst,
                   block_raw, elem_size, inverse)
 
 

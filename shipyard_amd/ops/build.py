@@ -20,7 +20,8 @@ ARCH = os.environ.get("SHIPYARD_GPU_ARCH", "gfx950")
 SOURCES = ["crc32c.hip", "lz4_decode.hip", "sha256.hip",
            "gather_copy.hip", "stager.cpp", "lz4_compress.cpp",
            "lz4_compress_gpu.hip", "byte_shuffle.hip",
-           "delta_filter.hip"]
+           "delta_filter.hip", "bit_shuffle.hip"]
+HEADERS = ["common.h", "shuffle_tile.h"]
 
 
 def hipcc() -> str:
@@ -39,7 +40,7 @@ def needs_build() -> bool:
     if not LIB.exists():
         return True
     lib_mtime = LIB.stat().st_mtime
-    for src in SOURCES + ["common.h"]:
+    for src in SOURCES + HEADERS:
         if (CSRC / src).stat().st_mtime > lib_mtime:
             return True
     return False

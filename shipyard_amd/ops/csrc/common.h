@@ -49,7 +49,7 @@ static inline int sy_dispatch_rung(uint32_t raw_cap, F&& f) {
 }
 
 // Host side of the SYSHARD block filters (byte_shuffle.hip,
-// delta_filter.hip): one launch walks a buffer of block_raw-sized blocks
+// delta_filter.hip, bit_shuffle.hip): one launch walks a buffer of block_raw-sized blocks
 // whose last block may be short.
 
 // What the exported wrappers accept: blocks made of whole 4 KiB tiles,
