@@ -441,6 +441,20 @@ class ShardIndex:
         np.cumsum(self.table["raw_len"][:-1], out=out[1:])
         return out
 
+    def select_blocks(self, offs, lens):
+        """Sorted unique ids (numpy int64) of the blocks that hold at
+        least one byte of the raw-space byte ranges
+        ``[offs[i], offs[i] + lens[i])``.  A range of length 0 selects
+        nothing.  ValueError for a negative offset or length and for a
+        range that ends past ``raw_size``.  Vectorized,
+        O(n_ranges + n_blocks): every block but the last holds exactly
+        ``block_raw`` bytes, so the block of a byte is a division, and
+        the union of the block intervals is a prefix sum over +1/-1
+        marks at their ends."""
+        offs, lens = _as_ranges(offs, lens, self.raw_size)
+        return _select_blocks(offs, lens, int(self.block_raw),
+                              self.n_blocks)
+
 
 def _align16(n: int) -> int:
     return (n + 15) & ~15
@@ -882,18 +896,20 @@ def _verify_crcs_device(out, idx, dev) -> None:
         raise ValueError(f"GPU CRC mismatch in blocks {bad}")
 
 
-def _decode_blocks(d_comp, idx: ShardIndex, dev):
-    """Gather the stored blocks and LZ4-decode the others into a new
-    raw_size tensor (still filtered when the shard has filters)."""
+def _launch_block_decode(d_comp, comp_off, comp_len, raw_len, out, out_off,
+                         block_raw: int, dev) -> None:
+    """Decode the blocks described by four equally long numpy columns
+    from ``d_comp`` into ``out`` at ``out_off`` (int64): one gather_copy
+    for the stored ones (comp_len == raw_len), one lz4_decode_blocks for
+    the others.  Shared by the whole-shard reader, where the columns are
+    the table and its raw offsets, and the range reader, where they are
+    the selected rows and their scratch slots."""
     import numpy as np
     import torch
 
     from shipyard_amd import ops
 
-    t = idx.table
-    raw_offs = idx.raw_offs()
-    stored = t["comp_len"] == t["raw_len"]
-    out = torch.empty(idx.raw_size, dtype=torch.uint8, device=dev)
+    stored = comp_len == raw_len
 
     def to_dev(arr, dtype):
         return torch.from_numpy(np.ascontiguousarray(arr)).to(dev).view(
@@ -901,23 +917,33 @@ def _decode_blocks(d_comp, idx: ShardIndex, dev):
 
     if stored.any():
         ops.gather_copy(
-            d_comp, to_dev(t["comp_off"][stored].astype(np.int64),
-                           torch.int64),
-            out, to_dev(raw_offs[stored], torch.int64),
-            to_dev(t["raw_len"][stored].view(np.int32), torch.uint32))
+            d_comp, to_dev(comp_off[stored].astype(np.int64), torch.int64),
+            out, to_dev(out_off[stored], torch.int64),
+            to_dev(raw_len[stored].view(np.int32), torch.uint32))
     lz4 = ~stored
     if lz4.any():
         status = ops.lz4_decode_blocks(
             d_comp,
-            to_dev(t["comp_off"][lz4].astype(np.int64), torch.int64),
-            to_dev(t["comp_len"][lz4].view(np.int32), torch.uint32),
+            to_dev(comp_off[lz4].astype(np.int64), torch.int64),
+            to_dev(comp_len[lz4].view(np.int32), torch.uint32),
             out,
-            to_dev(raw_offs[lz4], torch.int64),
-            to_dev(t["raw_len"][lz4].view(np.int32), torch.uint32),
-            raw_cap=idx.block_raw)
+            to_dev(out_off[lz4], torch.int64),
+            to_dev(raw_len[lz4].view(np.int32), torch.uint32),
+            raw_cap=block_raw)
         if not ops.lz4_all_ok(status):
             raise ValueError(
                 f"GPU LZ4 decode failed: status={status.cpu().tolist()}")
+
+
+def _decode_blocks(d_comp, idx: ShardIndex, dev):
+    """Gather the stored blocks and LZ4-decode the others into a new
+    raw_size tensor (still filtered when the shard has filters)."""
+    import torch
+
+    t = idx.table
+    out = torch.empty(idx.raw_size, dtype=torch.uint8, device=dev)
+    _launch_block_decode(d_comp, t["comp_off"], t["comp_len"], t["raw_len"],
+                         out, idx.raw_offs(), idx.block_raw, dev)
     return out
 
 
@@ -957,6 +983,229 @@ def decode_device(d_comp, idx: ShardIndex, device, verify: bool = True):
     if verify:
         _verify_crcs_device(out, idx, device)
     return out
+
+
+# ------------------------------------------------------------ range reads
+def _as_ranges(offs, lens, raw_size: int):
+    """``offs``/``lens`` as two equally long 1-D numpy int64 arrays,
+    checked against ``raw_size``.  ValueError names the first bad
+    range."""
+    import numpy as np
+
+    offs = np.ascontiguousarray(offs, dtype=np.int64).reshape(-1)
+    lens = np.ascontiguousarray(lens, dtype=np.int64).reshape(-1)
+    if len(offs) != len(lens):
+        raise ValueError(
+            f"ranges: {len(offs)} offsets but {len(lens)} lengths")
+    raw_size = int(raw_size)
+    # off + len <= raw_size without forming a sum that could wrap
+    bad = (offs < 0) | (lens < 0) | (offs > raw_size)
+    bad |= lens > raw_size - np.minimum(offs, raw_size)
+    if bad.any():
+        i = int(np.argmax(bad))
+        raise ValueError(
+            f"ranges: range {i} (offset {int(offs[i])}, length "
+            f"{int(lens[i])}) is negative or ends past raw_size="
+            f"{raw_size}")
+    return offs, lens
+
+
+def _select_blocks(offs, lens, block_raw: int, n_blocks: int):
+    import numpy as np
+
+    if block_raw <= 0:
+        raise ValueError("shard index: block_raw must be positive")
+    live = lens > 0
+    first = offs[live] // block_raw
+    last = (offs[live] + lens[live] - 1) // block_raw
+    if len(last) and int(last.max()) >= n_blocks:
+        raise ValueError(
+            f"shard index: a range ends in block {int(last.max())} but "
+            f"the table has {n_blocks} blocks")
+    # +1 where an interval of blocks opens, -1 behind its last block
+    mark = np.bincount(first, minlength=n_blocks + 1) - \
+        np.bincount(last + 1, minlength=n_blocks + 1)
+    return np.nonzero(np.cumsum(mark[:n_blocks]) > 0)[0].astype(np.int64)
+
+
+def _scratch_offsets(offs, lens, sel, block_raw: int, n_blocks: int):
+    """Where every range starts in the compact buffer that holds
+    selected block ``sel[k]`` at ``k * block_raw`` (numpy int64).  A
+    range that spans several blocks selected all of them, and ``sel`` is
+    sorted, so they are neighbours in the buffer too and the range is
+    contiguous there.  An empty range gets 0."""
+    import numpy as np
+
+    if not len(sel):
+        return np.zeros(len(offs), dtype=np.int64)
+    slot = np.full(n_blocks, -1, dtype=np.int64)
+    slot[sel] = np.arange(len(sel), dtype=np.int64)
+    # an empty range at raw_size may name the block behind the last one
+    blk = np.minimum(offs // block_raw, n_blocks - 1)
+    return np.where(lens > 0, slot[blk] * block_raw + offs % block_raw, 0)
+
+
+def read_ranges_cpu(buf: bytes, offs, lens, verify: bool = True) -> bytes:
+    """CPU reference of the range readers: the raw-space byte ranges
+    ``[offs[i], offs[i] + lens[i])`` of the shard in ``buf``,
+    concatenated in the caller's order.  Only the blocks that hold a
+    byte of a range (``ShardIndex.select_blocks``) are decoded, have
+    their filters undone (one ``filter_chain_numpy`` call on the compact
+    buffer of selected blocks) and, with ``verify``, their CRC checked:
+    a corrupt block that no range touches goes unnoticed."""
+    import numpy as np
+
+    idx = read_index(buf)
+    elems = _filter_elems("shard index", vars(idx))
+    offs, lens = _as_ranges(offs, lens, idx.raw_size)
+    block_raw = int(idx.block_raw)
+    sel = _select_blocks(offs, lens, block_raw, idx.n_blocks)
+    if not len(sel):
+        return b""
+    t = idx.table[sel]
+    if (t["raw_len"][:-1] != block_raw).any() or \
+            not 1 <= int(t["raw_len"][-1]) <= block_raw:
+        raise ValueError("shard index: inner block raw_len != block_raw")
+    compact = bytearray((len(sel) - 1) * block_raw + int(t["raw_len"][-1]))
+    for k, (coff, clen, rlen) in enumerate(zip(
+            t["comp_off"].tolist(), t["comp_len"].tolist(),
+            t["raw_len"].tolist())):
+        comp = buf[idx.payload_off + coff:idx.payload_off + coff + clen]
+        raw = comp if clen == rlen else lz4py.decompress_block(comp, rlen)
+        if len(raw) != rlen:
+            raise ValueError("shard size mismatch")
+        compact[k * block_raw:k * block_raw + rlen] = raw
+    # the ragged final block of the shard, if selected, is last: the
+    # compact buffer is a regular block_raw buffer for the filters
+    data = filter_chain_numpy(bytes(compact), block_raw, elems, inverse=True)
+    if verify:
+        crcs = np.asarray(gf2.crc32c_chunks_numpy(data, block_raw),
+                          dtype=np.uint32)
+        bad = sel[crcs != t["crc"]]
+        if len(bad):
+            raise ValueError(
+                f"CRC mismatch in shard blocks {bad[:8].tolist()}")
+    src = _scratch_offsets(offs, lens, sel, block_raw, idx.n_blocks)
+    return b"".join(data[s:s + n]
+                    for s, n in zip(src.tolist(), lens.tolist()))
+
+
+def _check_rows(lens, row_stride: int, fill: int) -> None:
+    """The output arguments of a range read against its (checked)
+    lengths; ValueError before anything is read, made or launched."""
+    import numpy as np
+
+    if int(row_stride) < 0:
+        raise ValueError(f"row_stride={row_stride} must not be negative")
+    if not 0 <= int(fill) <= 255:
+        raise ValueError(f"fill={fill} is not a byte value")
+    if row_stride and len(lens) and int(lens.max()) > row_stride:
+        i = int(np.argmax(lens > row_stride))
+        raise ValueError(
+            f"ranges: range {i} has {int(lens[i])} bytes, more than "
+            f"row_stride={row_stride}")
+
+
+def _decode_ranges(d_comp, idx: ShardIndex, sel, comp_off, offs, lens,
+                   device, verify: bool, row_stride: int, fill: int):
+    """The device side of a range read, shared by
+    ``decode_ranges_device`` and ``ShardStager.stage_ranges``: decode,
+    unfilter, verify, gather.  ``sel`` are the selected block ids and
+    ``comp_off`` where their payload starts in ``d_comp`` (the table's
+    column for a full payload, rebased offsets for a partial one);
+    ``offs``/``lens`` are checked numpy int64 arrays, the index is
+    validated and ``_check_rows`` has passed."""
+    import numpy as np
+    import torch
+
+    from shipyard_amd import ops
+
+    n = len(offs)
+    row_stride = int(row_stride)
+    if n == 0:
+        return torch.empty((0, row_stride) if row_stride else 0,
+                           dtype=torch.uint8, device=device)
+    if row_stride:
+        out = torch.full((n, row_stride), int(fill), dtype=torch.uint8,
+                         device=device)
+        dst_off = np.arange(n, dtype=np.int64) * row_stride
+    else:
+        out = torch.empty(int(lens.sum()), dtype=torch.uint8, device=device)
+        dst_off = np.zeros(n, dtype=np.int64)
+        np.cumsum(lens[:-1], out=dst_off[1:])
+    if not len(sel):
+        return out  # nothing but empty ranges
+    block_raw = int(idx.block_raw)
+    t = idx.table[sel]
+    scratch = torch.empty(
+        (len(sel) - 1) * block_raw + int(t["raw_len"][-1]),
+        dtype=torch.uint8, device=device)
+    _launch_block_decode(
+        d_comp, comp_off, t["comp_len"], t["raw_len"], scratch,
+        np.arange(len(sel), dtype=np.int64) * block_raw, block_raw, device)
+    scratch = unfilter_chain_device(
+        scratch, block_raw, _filter_elems("shard index", vars(idx)),
+        borrowed=False)
+    if verify:
+        crcs = ops.crc32c_chunks(scratch, chunk_size=block_raw)
+        want = torch.from_numpy(
+            np.ascontiguousarray(t["crc"]).view(np.int32).copy())
+        eq = crcs.view(torch.int32).cpu() == want
+        if not bool(eq.all().item()):
+            bad = sel[(~eq).numpy()][:8].tolist()
+            raise ValueError(f"GPU CRC mismatch in blocks {bad}")
+    src_off = _scratch_offsets(offs, lens, sel, block_raw, idx.n_blocks)
+
+    def to_dev(arr):
+        return torch.from_numpy(np.ascontiguousarray(arr)).to(device)
+
+    ops.gather_ranges(scratch, to_dev(src_off), to_dev(lens),
+                      out.view(-1), to_dev(dst_off))
+    return out
+
+
+def decode_ranges_device(d_comp, idx: ShardIndex, offs, lens, device,
+                         verify: bool = True, row_stride: int = 0,
+                         fill: int = 0):
+    """Random-access read of an uploaded shard payload in HBM: the
+    raw-space byte ranges ``[offs[i], offs[i] + lens[i])``, decoding
+    only the blocks that hold a byte of them.
+
+    ``d_comp`` is the full payload on the device, as for
+    ``decode_device``.  The table is validated first (``validate_index``
+    against ``d_comp.numel()``), then the ranges are checked against
+    ``raw_size`` and ``row_stride``; each failure is a ValueError raised
+    before a tensor is made or a kernel launched.
+
+    The selected blocks (``ShardIndex.select_blocks``) are decoded into
+    a compact scratch tensor, selected block ``k`` at ``k * block_raw``:
+    one gather_copy for the stored ones, one lz4_decode_blocks for the
+    others.  The ids are sorted, so the shard's short final block, if
+    selected, is last, and the scratch is a regular ``block_raw`` buffer
+    for ``unfilter_chain_device`` and, with ``verify``, for
+    ``crc32c_chunks``, whose result is compared with the selected rows'
+    CRCs (a mismatch is a ValueError that names the shard's block ids).
+    Only those blocks are verified: a corrupt block that no range
+    touches goes unnoticed.  ``ops.gather_ranges`` then cuts the ranges
+    out of the scratch; the byte at raw offset ``r`` is at
+    ``slot(r // block_raw) * block_raw + r % block_raw`` there.
+
+    ``row_stride == 0``: a 1-D uint8 tensor of ``sum(lens)`` bytes, the
+    ranges in the caller's order.  ``row_stride > 0``: a
+    ``[n, row_stride]`` uint8 tensor, row ``i`` holding range ``i``
+    followed by ``fill`` bytes (ValueError if a range is longer).  No
+    ranges: an empty tensor and no launch.  All host work is vectorized
+    numpy, whatever the number of ranges and blocks.
+
+    Peak HBM on top of the payload, with S selected blocks and
+    R = sum(lens): ``S * block_raw + R`` with no filter or delta alone,
+    ``2 * S * block_raw + R`` when shuffle or bitshuffle is on."""
+    validate_index(idx, d_comp.numel(), for_gpu=True)
+    offs, lens = _as_ranges(offs, lens, idx.raw_size)
+    _check_rows(lens, row_stride, fill)
+    sel = _select_blocks(offs, lens, int(idx.block_raw), idx.n_blocks)
+    return _decode_ranges(d_comp, idx, sel, idx.table["comp_off"][sel],
+                          offs, lens, device, verify, row_stride, fill)
 
 
 def unpack_gpu(buf: bytes, device=None, verify: bool = True):

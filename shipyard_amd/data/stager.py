@@ -160,6 +160,112 @@ class ShardStager:
                     p.name, size, hdr.raw_size, sec, res.gbps)
         return out, res
 
+    def stage_ranges(self, path, offs, lens, row_stride: int = 0,
+                     fill: int = 0) -> "tuple":
+        """Stage the raw-space byte ranges ``[offs[i], offs[i] +
+        lens[i])`` of one SYSHARD file into HBM, reading and decoding
+        only the blocks that hold a byte of them.  Returns
+        (tensor, StageResult); the tensor is what
+        ``shardfmt.decode_ranges_device`` returns for the same
+        ``row_stride`` and ``fill``, and the two share their decode,
+        unfilter, verify and gather code.
+
+        The header and the block table are read and checked as in
+        ``stage_file``.  The selected blocks are grouped into runs of
+        consecutive block ids; each run's span of the payload is read
+        with ``os.preadv`` into one pinned buffer, every run at a
+        16-byte-aligned cursor (which keeps the blocks' own 16-byte
+        alignment), and the buffer goes up in one non-blocking copy on
+        the stager's stream.  Range staging always uses this Python read
+        path, also with ``native=True``: the native pipeline is built
+        for large sequential spans.  Bytes between two runs are not
+        read; only the selected blocks are decoded and verified.
+
+        ``StageResult.file_bytes`` counts the bytes actually read from
+        the file (header + table + run spans) and ``raw_bytes`` is
+        ``sum(lens)``.  A file that is not a SYSHARD is a ValueError."""
+        import os
+
+        import numpy as np
+
+        torch = self.torch
+        p = Path(path)
+        size = p.stat().st_size
+        t0 = time.perf_counter()
+        with open(p, "rb") as f:
+            head = f.read(shardfmt.HEADER.size)
+            if head[:8] != shardfmt.MAGIC:
+                raise ValueError(f"{p}: not a SYSHARD file")
+            if len(head) < shardfmt.HEADER.size:
+                raise ValueError(
+                    f"{p}: truncated inside the SYSHARD header")
+            hdr = shardfmt.parse_header(head)
+            table_bytes = shardfmt.ENTRY.size * hdr.n_blocks
+            if size - shardfmt.HEADER.size < table_bytes:
+                raise ValueError(
+                    f"{p}: truncated inside the SYSHARD block table")
+            table = f.read(table_bytes)
+            if len(table) != table_bytes:
+                raise ValueError(
+                    f"{p}: truncated inside the SYSHARD block table")
+            payload_off = shardfmt.HEADER.size + table_bytes
+            idx = shardfmt.index_from_table(hdr, table)
+            # same order as decode_ranges_device: the table, the ranges,
+            # and only then anything that reads, allocates or launches
+            shardfmt.validate_index(idx, size - payload_off, for_gpu=True)
+            offs, lens = shardfmt._as_ranges(offs, lens, idx.raw_size)
+            shardfmt._check_rows(lens, row_stride, fill)
+            sel = idx.select_blocks(offs, lens)
+            comp_off = np.zeros(0, dtype=np.int64)
+            d_payload = None
+            span_total = 0
+            if len(sel):
+                t = idx.table[sel]
+                lo = t["comp_off"].astype(np.int64)
+                hi = lo + t["comp_len"]
+                # runs of consecutive ids; a run's span is everything
+                # from its lowest to its highest payload byte
+                opens = np.concatenate(([True], np.diff(sel) != 1))
+                starts = np.flatnonzero(opens)
+                span_lo = np.minimum.reduceat(lo, starts)
+                span_len = np.maximum.reduceat(hi, starts) - span_lo
+                cursor = np.zeros(len(starts), dtype=np.int64)
+                np.cumsum(((span_len + 15) & ~15)[:-1], out=cursor[1:])
+                run = np.cumsum(opens) - 1  # the run of every block
+                comp_off = lo - span_lo[run] + cursor[run]
+                span_total = int(span_len.sum())
+                # whole 16-byte groups, as the writers pad the payload
+                total = (int(cursor[-1] + span_len[-1]) + 15) & ~15
+                pin = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+                mv = memoryview(pin.numpy())
+                fd = f.fileno()
+                for c, o, n in zip(cursor.tolist(), span_lo.tolist(),
+                                   span_len.tolist()):
+                    got = 0
+                    while got < n:
+                        r = os.preadv(fd, [mv[c + got:c + n]],
+                                      payload_off + o + got)
+                        if not r:
+                            raise IOError(
+                                f"short read: wanted {n} bytes, got {got} "
+                                "(file truncated or concurrently shrunk)")
+                        got += r
+                with torch.cuda.stream(self.stream):
+                    d_payload = pin.to(self.device, non_blocking=True)
+        with torch.cuda.stream(self.stream):
+            out = shardfmt._decode_ranges(
+                d_payload, idx, sel, comp_off, offs, lens, self.device,
+                self.verify, row_stride, fill)
+        self.stream.synchronize()
+        sec = time.perf_counter() - t0
+        file_bytes = payload_off + span_total
+        res = StageResult(str(p), file_bytes, int(lens.sum()), sec,
+                          decoded=True, verified=self.verify)
+        logger.info("staged %d ranges of %s: read %d of %d bytes, %d raw "
+                    "bytes in %.3fs", len(lens), p.name, file_bytes, size,
+                    res.raw_bytes, sec)
+        return out, res
+
     def _decode(self, d_payload, idx: shardfmt.ShardIndex):
         import torch
 

@@ -119,6 +119,17 @@ def _load() -> ctypes.CDLL:
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
     ]
+    lib.sy_gather_range_pieces.restype = ctypes.c_int
+    lib.sy_gather_range_pieces.argtypes = [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_uint32, ctypes.c_void_p,
+    ]
+    lib.sy_gather_ranges.restype = ctypes.c_int
+    lib.sy_gather_ranges.argtypes = [
+        ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+        ctypes.c_void_p,
+    ]
     lib.sy_byte_shuffle.restype = ctypes.c_int
     lib.sy_byte_shuffle.argtypes = [
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32,
@@ -401,6 +412,73 @@ def gather_copy(src, src_off, dst, dst_off, lens):
         ctypes.c_void_p(dst_off.data_ptr()),
         ctypes.c_void_p(lens.data_ptr()), ctypes.c_uint32(n), _stream())
     _check(rc, "sy_gather_copy")
+
+
+def gather_ranges(src, src_off, lens, dst, dst_off):
+    """Ragged device gather: for every ``i``,
+    ``dst[dst_off[i]:dst_off[i]+lens[i]] = src[src_off[i]:src_off[i]+lens[i]]``.
+
+    ``src`` and ``dst`` are contiguous uint8 CUDA tensors on one device;
+    ``src_off``, ``lens`` and ``dst_off`` are int64 tensors of equal
+    length on that device.  Any byte alignment on either side (the
+    tensors' base pointers included), any length (0 too), ranges in any
+    order; source ranges may overlap or repeat.  A wrong dtype or device
+    of an offset tensor, or unequal lengths, is a ValueError raised
+    before any launch; no ranges at all is a no-op without a launch.
+
+    The caller guarantees, and nothing checks, that
+    * the destination ranges do not overlap each other,
+    * ``dst`` does not overlap ``src``,
+    * every range lies inside its tensor: the numbers are on the
+      device, and looking at them here would cost a synchronise
+      (``shardfmt.decode_ranges_device`` checks its ranges on the host,
+      where they come from).
+
+    Three launches, no host sync: the piece count of every range, its
+    prefix sum (``torch.cumsum``), and the gather, whose waves split the
+    bytes and not the ranges between them (gather_ranges.hip)."""
+    import torch
+
+    for t, which in ((src, "src"), (dst, "dst")):
+        assert t.dtype == torch.uint8 and t.is_contiguous(), \
+            f"gather_ranges: {which}"
+    for t, which in ((src_off, "src_off"), (lens, "lens"),
+                     (dst_off, "dst_off")):
+        if t.dtype != torch.int64:
+            raise ValueError(
+                f"gather_ranges: {which} must be int64, not {t.dtype}")
+        if t.dim() != 1 or not t.is_contiguous():
+            raise ValueError(
+                f"gather_ranges: {which} must be a contiguous 1-D tensor")
+        if t.device != src.device:
+            raise ValueError(
+                f"gather_ranges: {which} is on {t.device}, src on "
+                f"{src.device}")
+    n = lens.numel()
+    if src_off.numel() != n or dst_off.numel() != n:
+        raise ValueError(
+            f"gather_ranges: {src_off.numel()} source offsets, {n} "
+            f"lengths and {dst_off.numel()} destination offsets")
+    if n >= 1 << 32:
+        raise ValueError("gather_ranges: at most 2**32 - 1 ranges")
+    assert src.is_cuda and dst.is_cuda and src.device == dst.device, \
+        "gather_ranges: CUDA tensors on one device"
+    if n == 0:
+        return
+    lib = _load()
+    pieces = torch.empty(n, dtype=torch.int64, device=src.device)
+    rc = lib.sy_gather_range_pieces(
+        ctypes.c_void_p(dst.data_ptr()), ctypes.c_void_p(dst_off.data_ptr()),
+        ctypes.c_void_p(lens.data_ptr()), ctypes.c_void_p(pieces.data_ptr()),
+        ctypes.c_uint32(n), _stream())
+    _check(rc, "sy_gather_range_pieces")
+    cum = torch.cumsum(pieces, 0)
+    rc = lib.sy_gather_ranges(
+        ctypes.c_void_p(src.data_ptr()), ctypes.c_uint64(src.numel()),
+        ctypes.c_void_p(src_off.data_ptr()), ctypes.c_void_p(lens.data_ptr()),
+        ctypes.c_void_p(dst.data_ptr()), ctypes.c_void_p(dst_off.data_ptr()),
+        ctypes.c_void_p(cum.data_ptr()), ctypes.c_uint32(n), _stream())
+    _check(rc, "sy_gather_ranges")
 
 
 FILTER_ELEM_SIZES = (2, 4, 8)
