@@ -11,6 +11,7 @@ drives ``test_shard_edges_gpu.py`` and the stager tests.
 from __future__ import annotations
 
 import random
+from collections import namedtuple
 from typing import List, Tuple
 
 from shipyard_amd.data import lz4py
@@ -159,6 +160,307 @@ def decode_fuzz_blocks(raw_cap: int, seed: int, many_seq: bool
     last = rng.randint(raw_cap // 2, raw_cap - 1) | 1  # odd: never %16
     blocks.append(mixed_content(rng, last))
     return blocks
+
+
+# ------------------------------------------- hand-assembled decoder corpora
+# Streams the format allows but the project's greedy matchers never
+# emit.  A sequence is (literals, offset, mlen); the assembler encodes
+# it and builds the raw bytes without lz4py.
+SeqMark = namedtuple("SeqMark", "token off mext dlit dpos")
+SeqMark.__doc__ = (
+    "Positions of one assembled sequence: stream index of its token, of "
+    "its low offset byte and of its first match-length extension byte "
+    "(None without one); decoded position before its literals (dlit) "
+    "and before its match (dpos).")
+
+MATCH_OFFSETS = (1, 2, 3, 4, 5, 7, 8, 9, 15, 16, 17, 31, 32, 33, 63, 64, 65,
+                 66, 127, 128, 129, 255, 256, 257)
+MATCH_LENS = (4, 5, 15, 18, 19, 20, 63, 64, 65, 66, 127, 128, 129, 130, 191,
+              192, 193, 273, 274, 275, 529)
+REL_LENS = (5, 63, 64, 65, 128, 129)
+LIT_RUNS = (1, 0, 14, 15, 16, 63, 64, 65, 66, 127, 128, 129, 269, 270, 271,
+            525)
+FAR_REACH_RUNGS = (4096, 8192, 16384, 32768, 65536)
+DEEP_K = (1, 15, 16, 63, 64, 65)   # and the last sequence
+SEQ_CLASSES = ("lit_short", "lit_loop", "match_single", "match_loop",
+               "match_doubling_2", "match_doubling_3plus")
+
+
+def _lsic(out: bytearray, value: int) -> None:
+    while value >= 255:
+        out.append(255)
+        value -= 255
+    out.append(value)
+
+
+def assemble_lz4_marks(seqs, tail: bytes = b"", terminator: bool = None):
+    """-> (stream, raw, marks): ``assemble_lz4`` plus one SeqMark per
+    sequence.  ``terminator`` forces (True) or drops (False) the final
+    literals-only sequence; by default it is written iff ``tail`` is
+    not empty."""
+    stream, raw, marks = bytearray(), bytearray(), []
+    for lits, offset, mlen in seqs:
+        assert mlen >= 4 and 0 < offset <= 0xFFFF
+        token = len(stream)
+        dlit = len(raw)
+        stream.append((min(len(lits), 15) << 4) | min(mlen - 4, 15))
+        if len(lits) >= 15:
+            _lsic(stream, len(lits) - 15)
+        stream += lits
+        raw += lits
+        assert offset <= len(raw), "assembled offset reaches before 0"
+        off = len(stream)
+        stream.append(offset & 0xFF)
+        stream.append(offset >> 8)
+        mext = None
+        if mlen - 4 >= 15:
+            mext = len(stream)
+            _lsic(stream, mlen - 19)
+        marks.append(SeqMark(token, off, mext, dlit, len(raw)))
+        for _ in range(mlen):
+            raw.append(raw[-offset])
+    if terminator if terminator is not None else bool(tail):
+        stream.append(min(len(tail), 15) << 4)
+        if len(tail) >= 15:
+            _lsic(stream, len(tail) - 15)
+        stream += tail
+        raw += tail
+    else:
+        assert not tail
+    return bytes(stream), bytes(raw), marks
+
+
+def assemble_lz4(seqs, tail: bytes = b"", terminator: bool = None
+                 ) -> Tuple[bytes, bytes]:
+    """Encode ``seqs`` = [(literals, offset, mlen), ...] and the final
+    literals ``tail`` as one LZ4 block -> (stream, raw).  Writes token,
+    LSIC extension bytes, literals and the little-endian offset; raw is
+    built one byte at a time, independently of lz4py."""
+    stream, raw, _ = assemble_lz4_marks(seqs, tail, terminator)
+    return stream, raw
+
+
+def classify_sequences(seqs) -> List[Tuple[str, str]]:
+    """The branch of lz4_decode_kernel each sequence takes: (literal
+    class, match class), names from SEQ_CLASSES."""
+    out = []
+    for lits, offset, mlen in seqs:
+        lit = "lit_short" if len(lits) <= 64 else "lit_loop"
+        if offset >= mlen:
+            match = "match_single" if mlen <= 64 else "match_loop"
+        else:
+            done = rounds = 0
+            while done < mlen:
+                done += min(mlen - done, done + offset)
+                rounds += 1
+            match = "match_doubling_2" if rounds == 2 else \
+                "match_doubling_3plus"
+        out.append((lit, match))
+    return out
+
+
+def _match_off_spec(idx: int, offset: int):
+    """One match per MATCH_LENS at a fixed offset, behind a literal
+    prefix of 272 + idx >= 257 bytes.  Each further match follows 1, 2
+    or 3 literals, chosen (first hit of a depth-first search that tries
+    the three lengths in a rotating order) so that within the block the
+    matches start at every residue of dpos mod 16, and so mod 4."""
+    rng = random.Random(0x0FF5E7 + offset)
+    n_match = len(MATCH_LENS)
+
+    def search(j, dpos, seen, runs):
+        if len(seen) == 16:
+            # the rest keeps rotating through 1, 2, 3
+            return runs + [1 + (k + idx) % 3 for k in range(j, n_match)]
+        if n_match - j < 16 - len(seen):
+            return None
+        for t in range(3):
+            nlit = 1 + (j + idx + t) % 3
+            at = dpos + nlit
+            found = search(j + 1, at + MATCH_LENS[j], seen | {at % 16},
+                           runs + [nlit])
+            if found:
+                return found
+        return None
+
+    first = 272 + idx
+    runs = search(1, first + MATCH_LENS[0], {first % 16}, [first])
+    assert runs is not None and set(runs[1:]) == {1, 2, 3}
+    seqs = [(rng.randbytes(nlit), offset, mlen)
+            for nlit, mlen in zip(runs, MATCH_LENS)]
+    return seqs, rng.randbytes(1 + idx % 5)
+
+
+def _match_rel_spec():
+    rng = random.Random(0x4E1)
+    seqs, first = [], True
+    for mlen in REL_LENS:
+        for delta in (-1, 0, 1):
+            nlit = 136 if first else 1 + len(seqs) % 3
+            seqs.append((rng.randbytes(nlit), mlen + delta, mlen))
+            first = False
+    return seqs, rng.randbytes(2)
+
+
+def _lit_runs_spec():
+    rng = random.Random(0x117)
+    seqs, dpos = [], 0
+    for run in LIT_RUNS:
+        dpos += run
+        seqs.append((rng.randbytes(run), rng.randint(1, min(dpos, 300)), 4))
+        dpos += 4
+    return seqs, rng.randbytes(3)
+
+
+def _chain_spec(seed: int, n_seq: int, zero_lit: bool, max_mlen: int,
+                tail_len: int):
+    """An 8-byte literal prefix with a match, then ``n_seq`` sequences
+    of 0 (``zero_lit``) or 1..3 literals and a match of 4..max_mlen
+    bytes at a random legal offset."""
+    rng = random.Random(seed)
+    seqs, dpos = [], 0
+    for i in range(n_seq + 1):
+        nlit = 8 if i == 0 else 0 if zero_lit else 1 + i % 3
+        dpos += nlit
+        mlen = rng.randint(4, max_mlen)
+        seqs.append((rng.randbytes(nlit), rng.randint(1, dpos), mlen))
+        dpos += mlen
+    return seqs, rng.randbytes(tail_len)
+
+
+def _zero_lit_chain_spec():
+    return _chain_spec(0x2E80, 309, True, 12, 5)
+
+
+def _zero_lit_chain_short_spec():
+    # 100 four-byte matches: the longest chain that fits 448 raw bytes
+    return _chain_spec(0x2E81, 100, True, 4, 3)
+
+
+def _ordinary_chain_spec():
+    return _chain_spec(0x0DD, 210, False, 10, 4)
+
+
+def _ends_on_match_spec():
+    rng = random.Random(0xE0D)
+    return [(rng.randbytes(21), 7, 9), (rng.randbytes(2), 30, 70),
+            (b"", 3, 33)], b""
+
+
+def _small_mix_spec():
+    """Every match class in under 448 raw bytes."""
+    rng = random.Random(0x5A11)
+    return [(rng.randbytes(70), 3, 70),      # lit_loop, doubling 3+
+            (rng.randbytes(2), 100, 64),     # single
+            (rng.randbytes(1), 150, 100),    # loop
+            (rng.randbytes(3), 60, 100),     # doubling 2
+            (b"", 1, 19)], rng.randbytes(7)
+
+
+def assembled_specs():
+    """(name, seqs, tail, terminator) behind assembled_decode_blocks."""
+    specs = []
+    for idx, offset in enumerate(MATCH_OFFSETS):
+        specs.append(("match_off%d" % offset,
+                      *_match_off_spec(idx, offset), None))
+    specs.append(("match_rel", *_match_rel_spec(), None))
+    specs.append(("lit_runs", *_lit_runs_spec(), None))
+    specs.append(("zero_lit_chain", *_zero_lit_chain_spec(), None))
+    specs.append(("ends_on_match", *_ends_on_match_spec(), None))
+    specs.append(("empty", [], b"", None))
+    specs.append(("token_only", [], b"", True))
+    return specs
+
+
+def assembled_decode_blocks() -> List[Tuple[str, bytes, bytes]]:
+    """(name, stream, raw), at most 4096 raw bytes each:
+
+    * ``match_off<O>`` — for each O in MATCH_OFFSETS one match per
+      MATCH_LENS (token nibble 15 and extension ``00`` at 19, ``ff 00``
+      at 274, ``ff ff 00`` at 529);
+    * ``match_rel`` — offset == mlen - 1, mlen, mlen + 1 for REL_LENS;
+    * ``lit_runs`` — literal runs of LIT_RUNS bytes (extensions ``00``
+      at 15, ``ff 00`` at 270, ``ff ff 00`` at 525), each followed by a
+      minimum match;
+    * ``zero_lit_chain`` — 309 consecutive sequences without literals;
+    * ``ends_on_match`` — no trailing literals;
+    * ``empty`` — no stream at all; ``token_only`` — the stream ``00``."""
+    return [(name, *assemble_lz4(seqs, tail, term))
+            for name, seqs, tail, term in assembled_specs()]
+
+
+def far_reach(rung: int) -> Tuple[bytes, bytes, bytes]:
+    """-> (stream, raw, bad_stream).  ``rung - 68`` literals, then one
+    68-byte match with offset == dpos, the farthest legal reach: it
+    reads dst[0], ends on dst[rung - 1] and on the end of the stream.
+    ``bad_stream`` has offset == dpos + 1."""
+    rng = random.Random(0xFA2 ^ rung)
+    stream, raw, marks = assemble_lz4_marks(
+        [(rng.randbytes(rung - 68), rung - 68, 68)])
+    bad = bytearray(stream)
+    bad[marks[0].off:marks[0].off + 2] = (rung - 67).to_bytes(2, "little")
+    return stream, raw, bytes(bad)
+
+
+def small_decode_blocks() -> List[Tuple[str, bytes, bytes]]:
+    """Good blocks of at most 448 raw bytes for the slot-reuse launch."""
+    rng = random.Random(0x7121)
+    return [
+        ("tiny5", *assemble_lz4([], rng.randbytes(5))),
+        ("small_mix", *assemble_lz4(*_small_mix_spec())),
+        ("zero_lit_chain_short",
+         *assemble_lz4(*_zero_lit_chain_short_spec())),
+        ("ends_on_match", *assemble_lz4(*_ends_on_match_spec())),
+        ("empty", b"", b""),
+    ]
+
+
+def _deep_edits(chain: str, seqs, tail, ks
+                ) -> List[Tuple[str, bytes, int, int]]:
+    stream, raw, marks = assemble_lz4_marks(seqs, tail)
+    out = []
+    for k in ks:
+        m = marks[k]
+        tag = "%s_k%d_" % (chain, k)
+        zero = bytearray(stream)
+        zero[m.off:m.off + 2] = b"\0\0"
+        out.append((tag + "off0", bytes(zero), len(raw), ERR_OFFSET))
+        far = bytearray(stream)
+        far[m.off:m.off + 2] = (m.dpos + 1).to_bytes(2, "little")
+        out.append((tag + "off_gt_dpos", bytes(far), len(raw), ERR_OFFSET))
+        out.append((tag + "cut_offset", stream[:m.off + 1], len(raw),
+                    ERR_TRUNC))
+        # the same chain with a 274-byte match (extension ``ff 00``) at
+        # k, cut between the two extension bytes
+        long_seqs = list(seqs)
+        long_seqs[k] = (seqs[k][0], seqs[k][1], 274)
+        l_stream, l_raw, l_marks = assemble_lz4_marks(long_seqs, tail)
+        assert l_stream[l_marks[k].mext:l_marks[k].mext + 2] == b"\xff\x00"
+        out.append((tag + "cut_mlen_ext", l_stream[:l_marks[k].mext + 1],
+                    len(l_raw), ERR_TRUNC))
+        out.append((tag + "match_over_out", stream, m.dpos + 1,
+                    ERR_OVERFLOW))
+    out.append((chain + "_mismatch", stream, len(raw) + 1, ERR_MISMATCH))
+    assert tail
+    out.append((chain + "_lit_over_out", stream, len(raw) - 1,
+                ERR_OVERFLOW))
+    return out
+
+
+def deep_malformed_cases() -> List[Tuple[str, bytes, int, int]]:
+    """(name, stream, out_len, expected kernel status): one edit at
+    sequence k of ``zero_lit_chain`` and of a 211-sequence chain of
+    ordinary literal+match sequences, for k in DEEP_K and the last
+    sequence, so the error is met after the producer/consumer ring has
+    filled (k = 63, 64, 65) or wrapped several times (last).  Codes
+    follow the check order of lz4_decode.hip: offset TRUNC, match-length
+    TRUNC, OFFSET, match OVERFLOW inside the sequence; literal OVERFLOW
+    on the final literals; MISMATCH once the whole stream is parsed."""
+    out = []
+    for chain, (seqs, tail) in (("zero_lit", _zero_lit_chain_spec()),
+                                ("ordinary", _ordinary_chain_spec())):
+        out += _deep_edits(chain, seqs, tail, DEEP_K + (len(seqs) - 1,))
+    return out
 
 
 # ------------------------------------------------------ compressor corpora
@@ -338,3 +640,104 @@ def check_guarded_fuzz(raw_cap: int, pc: bool, seed: int) -> None:
         streams, [len(b) for b in blocks], raw_cap, pc)
     assert status == [OK] * len(blocks), status
     check_slots(got, stride, blocks)
+
+
+def _mismatches(names, status, codes):
+    return [(n, s, c) for n, s, c in zip(names, status, codes) if s != c]
+
+
+def check_assembled(raw_cap: int, pc: bool) -> None:
+    """Every assembled block in one launch: all OK, payloads exact,
+    guard bytes intact."""
+    blocks = assembled_decode_blocks()
+    names = [b[0] for b in blocks]
+    streams = [b[1] for b in blocks]
+    raws = [b[2] for b in blocks]
+    assert any(sum(map(len, streams[:i])) % 16 for i in range(len(streams)))
+    status, got, stride = guarded_decode(
+        streams, [len(r) for r in raws], raw_cap, pc)
+    assert status == [OK] * len(blocks), _mismatches(
+        names, status, [OK] * len(blocks))
+    check_slots(got, stride, raws)
+
+
+def check_deep_errors(pc: bool) -> None:
+    """good, bad, good, bad, ..., good at raw_cap = 4096 with the deep
+    malformed cases: exact codes, never DEADLOCK (6), bad slots
+    untouched, good payloads exact."""
+    good = assembled_decode_blocks()
+    names, streams, out_lens, expect, codes = [], [], [], [], []
+    for i, (name, stream, out_len, code) in enumerate(
+            deep_malformed_cases()):
+        g_name, g_stream, g_raw = good[i % len(good)]
+        names += [g_name, name]
+        streams += [g_stream, stream]
+        out_lens += [len(g_raw), out_len]
+        expect += [g_raw, b""]
+        codes += [OK, code]
+    names.append(good[-1][0])
+    streams.append(good[-1][1])
+    out_lens.append(len(good[-1][2]))
+    expect.append(good[-1][2])
+    codes.append(OK)
+    status, got, stride = guarded_decode(streams, out_lens, 4096, pc)
+    assert 6 not in status, _mismatches(names, status, codes)
+    assert status == codes, _mismatches(names, status, codes)
+    check_slots(got, stride, expect)
+
+
+def slot_reuse_launch(grid: int, full_chain: bool):
+    """-> (names, streams, out_lens, expected payloads, codes, stride)
+    for ``grid + 40`` blocks decoded by ``grid`` workgroups at raw_cap =
+    8192: blocks i and i + grid run back to back in one workgroup.  The
+    blocks cycle through small_decode_blocks(); six pairs (i, i + grid)
+    are a deep-error block and a good block, a TOOBIG block (out_len =
+    8193) and a good block, and a zero-literal chain and a 5-byte
+    block, each in both orders.  With ``full_chain`` the chain is
+    ``zero_lit_chain`` (four ring wraps) in slots of 4096 + 64 bytes;
+    without, its 100-sequence version, the longest that fits the 448
+    raw bytes of a 512-byte slot."""
+    small = small_decode_blocks()
+    by_name = {b[0]: b for b in small}
+    n = grid + 40
+    entries = [(*small[i % len(small)], None, OK) for i in range(n)]
+
+    def ok(block):
+        return (*block, None, OK)
+
+    tiny, good = ok(by_name["tiny5"]), ok(by_name["small_mix"])
+    if full_chain:
+        chain = ok(("zero_lit_chain",
+                    *assemble_lz4(*_zero_lit_chain_spec())))
+        stride = slot_stride(4096)
+    else:
+        chain = ok(by_name["zero_lit_chain_short"])
+        stride = 512
+    seqs, tail = _zero_lit_chain_short_spec()
+    stream, raw, marks = assemble_lz4_marks(seqs, tail)
+    bad = bytearray(stream)
+    bad[marks[65].off:marks[65].off + 2] = b"\0\0"
+    deep = ("deep_off0_k65", bytes(bad), b"", len(raw), ERR_OFFSET)
+    toobig = ("toobig", good[1], b"", 8193, ERR_TOOBIG)
+    pairs = [(deep, good), (good, deep), (toobig, good), (good, toobig),
+             (chain, tiny), (tiny, chain)]
+    for i, (first, second) in zip((1, 7, 13, 20, 29, 38), pairs):
+        assert i + grid < n
+        entries[i], entries[i + grid] = first, second
+    names = [e[0] for e in entries]
+    streams = [e[1] for e in entries]
+    expect = [e[2] for e in entries]
+    out_lens = [len(e[2]) if e[3] is None else e[3] for e in entries]
+    codes = [e[4] for e in entries]
+    assert all(len(p) <= stride - SLOT_SLACK for p in expect)
+    return names, streams, out_lens, expect, codes, stride
+
+
+def check_slot_reuse(grid: int, pc: bool, full_chain: bool) -> None:
+    """One launch of slot_reuse_launch: exact status list, exact slots."""
+    names, streams, out_lens, expect, codes, stride = slot_reuse_launch(
+        grid, full_chain)
+    status, got, stride = guarded_decode(streams, out_lens, 8192, pc,
+                                         stride=stride)
+    assert status == codes, _mismatches(names, status, codes)
+    check_slots(got, stride, expect)

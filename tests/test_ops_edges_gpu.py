@@ -316,6 +316,102 @@ class TestLz4DecodeEdges:
             corpus.guarded_decode([stream], [out_len], 65537, pc,
                                   stride=corpus.slot_stride(65536))
 
+    @pytest.mark.parametrize("pc", [False, True])
+    def test_assembled_streams(self, pc):
+        """Hand-assembled streams no greedy matcher emits, one launch at
+        raw_cap = 4096: every offset/length relation of the match copy
+        (single, strided loop, doubling with two and with many rounds),
+        both literal paths, every length-extension shape, a 309-long
+        chain of zero-literal sequences, a stream ending on a match, the
+        empty stream and the lone token."""
+        corpus.check_assembled(4096, pc)
+
+    @pytest.mark.parametrize("pc", [False, True])
+    @pytest.mark.parametrize("raw_cap", _RAW_CAPS)
+    def test_far_reach(self, raw_cap, pc):
+        """offset == dpos: the match reads dst[0] and ends on the last
+        byte of the block and of the stream; offset == dpos + 1 in the
+        next slot is ERR_OFFSET and leaves the slot untouched.  On the
+        single-wave kernel the match ends on dst[RAWCAP - 1].  pc has no
+        4 KiB or 32 KiB rung (lz4_decode.hip), so there raw_cap = 4096
+        and 32768 end in the middle of dst[8192] and dst[65536]."""
+        cap = _pc_effective_cap(raw_cap) if pc else raw_cap
+        stream, raw, bad = corpus.far_reach(raw_cap)
+        status, got, stride = corpus.guarded_decode(
+            [stream, bad], [raw_cap, raw_cap], raw_cap, pc,
+            stride=corpus.slot_stride(cap))
+        assert status == [corpus.OK, corpus.ERR_OFFSET]
+        corpus.check_slots(got, stride, [raw, b""])
+
+    @pytest.mark.parametrize("pc", [False, True])
+    def test_deep_errors_in_mixed_launch(self, pc):
+        """Errors at sequence 1, 15, 16, 63, 64, 65 and the last one of
+        a zero-literal chain and of an ordinary chain, interleaved with
+        good blocks.  The codes are those of
+        test_error_codes_in_mixed_launch's check order on both kernels;
+        in lz4_decode_pc_kernel the producer raises them with a full or
+        wrapped ring while the consumer still holds unread records, and
+        no block may report DEADLOCK (6)."""
+        corpus.check_deep_errors(pc)
+
+    def test_pc_workgroup_decodes_second_block(self):
+        """4096 + 40 blocks on the 4096-workgroup pc grid at raw_cap =
+        8192: workgroup w decodes blocks w and w + 4096 and reuses dst,
+        sbuf, ring and ctl.  Pairs, in both orders: deep-error block and
+        good block (ctl[2] reset), TOOBIG block and good block (the
+        `__syncthreads(); continue;` path), zero-literal chain and
+        5-byte block (ring counters, short block in a used dst).
+
+        First launch: blocks of at most 448 raw bytes in 512-byte slots;
+        300 zero-literal sequences need 1200 raw bytes, so the chain
+        here has 100 sequences (one ring wrap).  Second launch: the same
+        pattern with the full ``zero_lit_chain`` in 4160-byte slots."""
+        corpus.check_slot_reuse(4096, True, full_chain=False)
+        corpus.check_slot_reuse(4096, True, full_chain=True)
+
+    @pytest.mark.parametrize("nostage", [None, "0"])
+    def test_single_wave_workgroup_decodes_second_block_in_child(
+            self, nostage):
+        """SY_LZ4_GRID is read once per process: a fresh child with
+        SY_LZ4_GRID=3 decodes 3 + 40 blocks, so every workgroup of
+        lz4_decode_kernel makes 14 or 15 trips through its block loop
+        over the pairs of test_pc_workgroup_decodes_second_block (full
+        ``zero_lit_chain``).  The second child adds SY_LZ4_NOSTAGE=0:
+        the staged instantiation reuses sbuf as well.  Both children
+        also decode the assembled blocks and the deep-error launch, in
+        three trips per workgroup or more.
+
+        The cap cannot be observed from outside (a capped and an
+        uncapped launch write the same bytes), so the test also pins
+        that the host wrapper still reads the variable under this name;
+        the child checks that it arrived."""
+        here = os.path.dirname(os.path.abspath(__file__))
+        root = os.path.dirname(here)
+        with open(os.path.join(root, "shipyard_amd", "ops", "csrc",
+                               "lz4_decode.hip")) as f:
+            assert 'sy_env_atoi("SY_LZ4_GRID", 0)' in f.read()
+        code = (
+            "import sys\n"
+            "sys.path[:0] = [%r, %r]\n"
+            "import ops_edge_corpus as c\n"
+            "from shipyard_amd import ops\n"
+            "assert ops._env_atoi('SY_LZ4_GRID', 0) == 3\n"
+            "c.check_slot_reuse(3, False, full_chain=True)\n"
+            "c.check_slot_reuse(3, False, full_chain=False)\n"
+            "c.check_assembled(4096, False)\n"
+            "c.check_deep_errors(False)\n"
+            "print('OK')\n" % (here, root))
+        env = {k: v for k, v in os.environ.items() if k != "SY_LZ4_NOSTAGE"}
+        env["SY_LZ4_GRID"] = "3"
+        if nostage is not None:
+            env["SY_LZ4_NOSTAGE"] = nostage
+        # four small launches + interpreter and torch start-up
+        res = subprocess.run(
+            [sys.executable, "-c", code], env=env, timeout=300,
+            capture_output=True, text=True)
+        assert res.returncode == 0, res.stdout + res.stderr
+        assert res.stdout.strip().splitlines()[-1] == "OK"
+
 
 # --------------------------------------------------------- GPU compressors
 def _gpu_compress(data: bytes, block_raw: int, screen: bool):
@@ -392,6 +488,62 @@ class TestGpuCompressorEdges:
         data = _cuda(_seeded(7, 65536 + 4096))
         with pytest.raises(RuntimeError, match="-22"):
             ops.lz4_compress_blocks_gpu(data, 65536 + 4096, screen=screen)
+
+    @pytest.mark.parametrize("block_raw", [12288, 61440])
+    def test_off_rung_block_sizes(self, block_raw):
+        """block_raw between rungs: 12 KiB runs the 16 KiB and 60 KiB
+        the 64 KiB instantiations of both matchers and of both decoders
+        with every block shorter than RAWCAP.  The serial matcher is
+        byte-identical to the CPU compressor, the screen matcher
+        round-trips through lz4py, and the device slots of both decode
+        on the GPU with raw_cap = block_raw into guarded slots."""
+        from shipyard_amd import ops
+
+        data = _seeded(block_raw + 2, 3 * block_raw + 1234)
+        raws = _raw_blocks(data, block_raw)
+        cpu = ops.lz4_compress_blocks(data, block_raw)
+        assert len(raws) == len(cpu) == 4
+        for screen in (False, True):
+            blobs, d_out, stride, lens = _gpu_compress(
+                data, block_raw, screen)
+            if not screen:
+                assert blobs == cpu
+            kept = [b for b, blob in enumerate(blobs) if blob is not None]
+            assert kept, "no compressible block"
+            for b in kept:
+                assert len(blobs[b]) < len(raws[b]), (screen, b)
+                assert lz4py.decompress_block(
+                    blobs[b], len(raws[b])) == raws[b], (screen, b)
+            dev = d_out.device
+            slot = corpus.slot_stride(block_raw)
+            t64 = lambda v: torch.tensor(v, dtype=torch.int64, device=dev)
+            t32 = lambda v: torch.tensor(v, dtype=torch.int64).to(
+                torch.uint32).to(dev)
+            for pc in (False, True):
+                out = torch.full((len(kept) * slot,), corpus.GUARD,
+                                 dtype=torch.uint8, device=dev)
+                status = ops.lz4_decode_blocks(
+                    d_out, t64([b * stride for b in kept]),
+                    t32([int(lens[b]) for b in kept]), out,
+                    t64([i * slot for i in range(len(kept))]),
+                    t32([len(raws[b]) for b in kept]), raw_cap=block_raw,
+                    pc=pc)
+                torch.cuda.synchronize()
+                assert ops.lz4_all_ok(status), (screen, pc, status.cpu())
+                corpus.check_slots(out.cpu().numpy(), slot,
+                                   [raws[b] for b in kept])
+
+    def test_shard_roundtrip_at_block_raw_12288(self):
+        """shardfmt.pack_gpu then unpack_gpu at a block size between the
+        8 and 16 KiB rungs returns the input (CRC-verified)."""
+        from shipyard_amd.data import shardfmt
+
+        data = _seeded(12288, 3 * 12288 + 1234)
+        blob = shardfmt.pack_gpu(data, block_raw=12288)
+        assert shardfmt.read_index(blob).block_raw == 12288
+        got = shardfmt.unpack_gpu(blob)
+        assert bytes(got.cpu().numpy().tobytes()) == data
+        assert shardfmt.unpack_cpu(blob) == data
 
     @pytest.mark.parametrize("screen", [False, True])
     def test_encoding_edges(self, screen):
