@@ -322,12 +322,18 @@ def lz4_compress_blocks_gpu(data, block_raw: int,
     stride, uint32 lens CPU tensor) — lens[b] == 0 means
     incompressible (store raw).  The staging loop loads uint4 from
     ``data``'s base: it must be contiguous and 16-byte aligned
-    (ValueError before launch otherwise)."""
+    (ValueError before launch otherwise).  Every block starts at a
+    multiple of ``block_raw``, so ``block_raw`` must be a positive
+    multiple of 16 for the same reason (ValueError as well)."""
     if screen is None:
         screen = os.environ.get("SHIPYARD_LZ4C_SCREEN", "1") == "1"
 
     import torch
 
+    if block_raw <= 0 or block_raw % 16:
+        raise ValueError(
+            f"lz4_compress_blocks_gpu: block_raw must be a positive "
+            f"multiple of 16 (uint4 staging loads), got {block_raw}")
     _check_u8_device(data, "lz4_compress_blocks_gpu")
     lib = _load()
     n = data.numel()

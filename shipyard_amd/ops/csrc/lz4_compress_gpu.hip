@@ -50,10 +50,12 @@ __device__ __forceinline__ uint32_t lds_rd32(const uint8_t* sbuf,
   return sh ? ((lo >> sh) | (hi << (32u - sh))) : lo;
 }
 
-// stage the source block into LDS (coalesced 16 B/lane; in_off is
-// block_raw-aligned from the wrapper, so uint4 loads are aligned;
-// the ragged tail copies bytewise so the last block never reads
-// past the input tensor)
+// stage the source block into LDS (coalesced 16 B/lane).  The uint4
+// loads need data + in_off 16-byte aligned: the wrapper passes an
+// aligned base and in_off = blk * block_raw, and rejects a block_raw
+// that is not a positive multiple of 16; a caller of the C entry
+// points owes the same.  The ragged tail copies bytewise so the last
+// block never reads past the input tensor.
 __device__ __forceinline__ void stage_block(uint8_t* sbuf,
                                             const uint8_t* gsrc, uint32_t n,
                                             int lane) {
@@ -201,8 +203,9 @@ __global__ __launch_bounds__(SY_WAVE) void lz4_compress_kernel(
 // greedy-LZ4 stream, but NOT byte-identical to v1 — candidates whose
 // source lies inside the current 64-position batch are invisible
 // (their inserts land after the screen), so some short-range matches
-// shift by a batch.  Tests assert decode-roundtrip + ratio bounds
-// instead.
+// shift by a batch.  The stream is deterministic all the same: tests
+// compare it byte for byte with a Python model of this policy
+// (tests/lz4_match_model.py), as they do the serial matcher's.
 // ---------------------------------------------------------------------
 template <int RAWCAP>
 __global__ __launch_bounds__(SY_WAVE) void lz4_compress_screen_kernel(

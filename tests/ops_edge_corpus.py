@@ -515,6 +515,478 @@ def final_block(data: bytes, block_raw: int) -> bytes:
     return data[(n_blocks - 1) * block_raw:]
 
 
+# --------------------------------------------------------- matcher corpora
+# Blocks built for single branches of lz4_compress_kernel and
+# lz4_compress_screen_kernel.  Every builder draws seeded candidates and
+# keeps the first one whose model trace (lz4_match_model) shows the
+# feature for BOTH policies, so a table entry lost to a chance hash
+# collision in the filler cannot hollow a case out; MATCHER_FEATURES
+# holds the same predicates for the CPU pins.
+MATCHER_RUNGS = (4096, 8192, 16384, 32768, 65536)
+EXT_MISS_K = (0, 1, 63, 64, 65, 127, 128, 129)
+# A match that ends on match_limit = n - 5 starts at or before
+# mflimit = n - 12, so it has at least 7 bytes: k = mlen - 4 = 3 is the
+# smallest case that exists (the match starts exactly at mflimit).
+EXT_LIMIT_K = (3, 63, 64, 65, 127, 128, 129)
+PERIODS = (2, 3, 5, 16, 17, 63, 64, 65)
+FAR_D = (0, 1, 4)
+DROP_STEPS = ("token", "litlen", "literals", "offset", "mlen")
+# Cases whose feature depends on the block's own length: it is lost when
+# the block is zero-padded to a slot, and holds where the kernel is
+# given the true length (a direct launch, or the last block of a
+# wrapper launch).
+SHORT_PREFIXES = ("fit_", "drop_at_", "tail_", "full_minus_1")
+
+
+def is_short_case(name: str) -> bool:
+    return name.startswith(SHORT_PREFIXES)
+
+
+def pad_slot(block: bytes, rung: int) -> bytes:
+    assert len(block) <= rung
+    return block + b"\0" * (rung - len(block))
+
+
+def _traces(block: bytes, keep_all: bool = False):
+    """-> ((greedy stream, trace), (screen stream, trace))"""
+    import lz4_match_model as model
+
+    gt, st = {}, {}
+    g = model.greedy_model(block, gt, keep_all=keep_all)
+    s = model.screen_model(block, st, keep_all=keep_all)
+    return (g, gt), (s, st)
+
+
+def _both(block: bytes, pred) -> bool:
+    (_, gt), (_, st) = _traces(block)
+    return pred(gt) and pred(st)
+
+
+def _any_match(**want):
+    def pred(trace):
+        return any(all(m.get(k) == v for k, v in want.items())
+                   for m in trace["matches"])
+    return pred
+
+
+def _feat_period(period: int):
+    def pred(trace):
+        m = trace["matches"]
+        return bool(m) and m[0]["offset"] == period < m[0]["mlen"]
+    return pred
+
+
+def _feat_far(n: int, d: int):
+    def pred(trace):
+        m = trace["matches"]
+        return bool(m) and (m[-1]["pos"], m[-1]["offset"]) == (
+            n - 12 - d, n - 12 - d)
+    return pred
+
+
+def _feat_collide(trace) -> bool:
+    # A ... B ... A: B probes A's entry, the second A probes B's, both
+    # are rejected by the compare and the second A starts no match
+    seen = trace["collisions"]
+    chain = [(p2, r2) for p1, r1 in seen for p2, r2 in seen if r2 == p1]
+    starts = {m["pos"] for m in trace["matches"]}
+    return any(p2 not in starts for p2, _ in chain)
+
+
+def _feat_screen_rounds(check):
+    def pred(block: bytes) -> bool:
+        (_, _), (_, st) = _traces(block)
+        return check(st, len(block))
+    return pred
+
+
+def _feat_two_hits(st, n) -> bool:
+    return any(len(r["cands"]) >= 2 and
+               r["inserted"] == r["j"] + 1 < r["in_range"]
+               for r in st["rounds"])
+
+
+def _feat_last_lane(st, n) -> bool:
+    return any(m["pos"] == n - 12 and m["lane"] == m["in_range"] - 1 < 63
+               for m in st["matches"])
+
+
+def _feat_dry_exit(st, n) -> bool:
+    last = st["rounds"][-1]
+    return (bool(st["matches"]) and st["drop"] is None and
+            last["j"] is None and last["pos"] + 64 > n - 12 >= last["pos"])
+
+
+def _feat_two_dry(st, n) -> bool:
+    js = [r["j"] for r in st["rounds"][:3]]
+    return len(js) == 3 and js[0] is None and js[1] is None and \
+        js[2] is not None
+
+
+def _feat_batch_blind(block: bytes) -> bool:
+    (g, gt), (s, st) = _traces(block)
+    blind = {m["pos"] for m in gt["matches"]} - \
+        {m["pos"] for m in st["matches"]}
+    # the match only the serial policy sees has its source in the same
+    # 64-position round
+    return g != s and bool(blind) and any(
+        m["pos"] in blind and m["pos"] // 64 == m["src"] // 64
+        for m in gt["matches"]) and not any(
+        r["j"] is not None and r["pos"] <= min(blind) < r["pos"] + 64
+        for r in st["rounds"])
+
+
+def _fit_delta(block: bytes):
+    (g, _), (s, _) = _traces(block, keep_all=True)
+    return len(g) - len(block), len(s) - len(block)
+
+
+def matcher_feature(name: str):
+    """-> predicate(block) -> bool: the block reaches the feature the
+    case ``name`` stands for, under both match models unless the case
+    is about one of them.  None for cases defined by their size alone
+    (``zeros_full``, ``tail_<n>``, ``full_*``), which the pins check
+    directly."""
+    def both(pred):
+        return lambda block: _both(block, pred)
+
+    if name.startswith("residue_"):
+        return both(_any_match(pos_mod4=int(name[8]), src_mod4=int(name[9])))
+    if name.startswith("ext_"):
+        _, k, end = name.split("_")
+        return both(_any_match(mlen=int(k) + 4, end=end))
+    if name.startswith("period_"):
+        return both(_feat_period(int(name[7:])))
+    if name.startswith("far_"):
+        return lambda block: _both(block, _feat_far(len(block),
+                                                    int(name[4:])))
+    if name == "collide":
+        return both(_feat_collide)
+    if name == "reprime_only":
+        return both(_any_match(via_reprime=True))
+    if name.startswith("fit_"):
+        delta = {"m1": -1, "0": 0, "p1": 1}[name[4:]]
+        return lambda block: 40 <= len(block) <= 120 and \
+            _fit_delta(block) == (delta, delta)
+    if name.startswith("drop_at_"):
+        step = name[8:]
+        return both(lambda trace: trace["drop"] == step)
+    if name in ("lane_0", "lane_63"):
+        lane = int(name[5:])
+        return _feat_screen_rounds(lambda st, n: any(
+            m["lane"] == lane and m["in_range"] == 64
+            for m in st["matches"]))
+    return {
+        "last_lane_mflimit": _feat_screen_rounds(_feat_last_lane),
+        "two_dry_then_hit": _feat_screen_rounds(_feat_two_dry),
+        "two_hits": _feat_screen_rounds(_feat_two_hits),
+        "batch_blind": _feat_batch_blind,
+        "dry_exit": _feat_screen_rounds(_feat_dry_exit),
+    }.get(name)
+
+
+def _pick(name: str, seed: int, build, tries: int = 400) -> bytes:
+    """First seeded candidate of ``build(rng)`` that reaches the feature
+    of ``name``."""
+    rng = random.Random(seed)
+    reaches = matcher_feature(name)
+    for _ in range(tries):
+        block = build(rng)
+        if block is not None and reaches(block):
+            return block
+    raise AssertionError("no %s block in %d tries" % (name, tries))
+
+
+def _pick_kept(seed: int, n: int) -> bytes:
+    """Seeded mixed content of ``n`` bytes that both matchers keep."""
+    rng = random.Random(seed)
+    while True:
+        block = mixed_content(rng, n)
+        (g, _), (s, _) = _traces(block)
+        if g is not None and s is not None:
+            return block
+
+
+def _repeat_block(rng, src_at: int, pos: int, piece: bytes, n: int = None
+                  ) -> bytes:
+    """Random filler with ``piece`` at ``src_at`` and again at ``pos``;
+    the byte behind each copy differs.  Without ``n`` a 128-byte run
+    and 16 filler bytes follow the second copy, so the block is kept;
+    with ``n`` the filler in front of the first copy starts with
+    zeros for the same reason, where there is room."""
+    if n is None:
+        n = pos + len(piece) + 160
+        buf = bytearray(rng.randbytes(n))
+        buf[n - 144:n - 16] = b"\xEE" * 128
+    else:
+        buf = bytearray(rng.randbytes(n))
+        if src_at > 256:
+            buf[:src_at - 128] = bytes(src_at - 128)
+    buf[src_at:src_at + len(piece)] = piece
+    buf[pos:pos + len(piece)] = piece
+    if pos + len(piece) < n:
+        buf[pos + len(piece)] = buf[src_at + len(piece)] ^ 0x55
+    return bytes(buf[:n])
+
+
+def _residue_block(a: int, b: int):
+    return lambda rng: _repeat_block(rng, 4 + b, 128 + a, rng.randbytes(11))
+
+
+def _ext_miss_block(k: int):
+    def build(rng):
+        piece = rng.randbytes(4 + k)
+        pos = 64 * ((8 + len(piece)) // 64 + 2) + 9
+        return _repeat_block(rng, 8, pos, piece)
+    return build
+
+
+def _ext_limit_block(k: int, n: int):
+    def build(rng):
+        # the copy runs to the end of the block, so only match_limit
+        # ends the extension after mlen = 4 + k bytes
+        piece = rng.randbytes(4 + k + 5)
+        pos = n - len(piece)
+        return _repeat_block(rng, pos - len(piece) - 70, pos, piece, n)
+    return build
+
+
+def _period_block(period: int):
+    def build(rng):
+        pat = bytes(rng.sample(range(256), period))
+        body = (pat * (300 // period + 1))[:300]
+        return rng.randbytes(8) + body + rng.randbytes(16)
+    return build
+
+
+def _far_block(n: int, d: int):
+    def build(rng):
+        probe = bytes(rng.sample(range(1, 256), 8))
+        buf = bytearray(n)
+        buf[:8] = probe
+        q = n - 12 - d
+        buf[q:q + 8] = probe
+        rest = [v for v in range(1, 256) if v not in probe]
+        buf[q + 8:] = bytes(rng.sample(rest, n - q - 8))
+        assert len(buf) == n and len(set(buf[-5:])) == 5
+        return bytes(buf)
+    return build
+
+
+def _collide_block(rng):
+    import lz4_match_model as model
+
+    seen = {}
+    while True:
+        v = rng.getrandbits(32)
+        other = seen.setdefault(model.hash4(v), v)
+        if other != v:
+            break
+    a, b = v.to_bytes(4, "little"), other.to_bytes(4, "little")
+    buf = bytearray(rng.randbytes(160))
+    buf[8:12], buf[72:76], buf[136:140] = a, b, a
+    return bytes(buf) + b"\xEE" * 128 + rng.randbytes(16)
+
+
+def _reprime_block(rng):
+    # M ... M[:18] Z ...: the second M is an 18-byte match, the reprime
+    # inserts the 4-gram M[16:18] + Z[:2] that lies inside the skipped
+    # span; the only later copy of that 4-gram finds it there
+    m, z = rng.randbytes(20), rng.randbytes(8)
+    tail = m[16:18] + z
+    return (rng.randbytes(8) + m + rng.randbytes(56) + m[:18] + z +
+            rng.randbytes(70) + tail + rng.randbytes(16))
+
+
+def _fit_block(rng):
+    # 64..90 literals, a match of 4..6 bytes from the block's start, a
+    # final run below 15 bytes: token + extension byte + offset + final
+    # token cost 5 bytes against the 4..6 the match saves
+    lits, mlen, rest = rng.randint(64, 90), rng.randint(4, 6), \
+        rng.randint(8, 14)
+    return _repeat_block(rng, 0, lits, rng.randbytes(mlen),
+                         lits + mlen + rest)
+
+
+def _drop_block(step: str, rung: int):
+    """One literal run long enough that its length-extension bytes push
+    ``opos`` to ``cap`` at the named step of the match sequence (or of
+    the final literals) behind it."""
+    if step == "literals":
+        return lambda rng: rng.randbytes(100)
+    mlen, rest = {"token": (4, 8), "litlen": (4, 15), "offset": (4, 8),
+                  "mlen": (19, 5)}[step]
+
+    def build(rng):
+        lits = 15 + 255 * rng.randint(0, 21)
+        n = lits + mlen + rest
+        if n > rung:
+            return None
+        return _repeat_block(rng, 0, lits, rng.randbytes(mlen), n)
+    return build
+
+
+def _last_lane_block(n: int):
+    def build(rng):
+        piece = rng.randbytes(12)
+        return _repeat_block(rng, n - 12 - 100, n - 12, piece, n)
+    return build
+
+
+def _two_hits_block(rng):
+    buf = bytearray(rng.randbytes(190))
+    p1, p2 = rng.randbytes(12), rng.randbytes(12)
+    buf[8:20], buf[24:36] = p1, p2
+    buf[130:142], buf[150:162] = p1, p2
+    return bytes(buf)
+
+
+def _batch_blind_block(rng):
+    buf = bytearray(rng.randbytes(200))
+    buf[100:112] = buf[70:82]
+    return bytes(buf) + b"\xEE" * 128 + rng.randbytes(16)
+
+
+def _dry_exit_block(n: int):
+    return lambda rng: b"\0" * (n - 196) + rng.randbytes(196)
+
+
+_MATCHER_CACHE = {}
+
+
+def matcher_blocks(rung: int) -> List[Tuple[str, bytes]]:
+    """(name, block) inputs for both GPU matchers, each block at most
+    ``rung`` bytes.  Cases that need no size exist at the 4 KiB rung
+    only; ``zeros_full``, ``far_<d>``, ``drop_at_<step>``,
+    ``full_minus_1`` and ``full_exact`` at every rung (``drop_at_mlen``
+    needs 5.1 KiB of literals, so from 8 KiB up).
+
+    Both matchers
+    * ``residue_<a><b>`` — a match at pos % 4 == a from r % 4 == b;
+    * ``ext_<k>_miss`` / ``ext_<k>_limit`` — a match of 4 + k bytes
+      ended by a differing byte / by match_limit (block of ``rung``
+      bytes, the copy runs to its end);
+    * ``zeros_full`` — ``rung`` zero bytes;
+    * ``period_<P>`` — 300 bytes of period P behind 8 random bytes;
+    * ``far_<d>`` — probe at 0, zeros, the probe again at n - 12 - d;
+    * ``collide`` — A ... B ... A with hash4(A) == hash4(B);
+    * ``reprime_only`` — a match whose table entry only the reprime
+      wrote;
+    * ``fit_m1`` / ``fit_0`` / ``fit_p1`` — 40..120 bytes, the stream of
+      either matcher is n - 1 / n / n + 1 bytes;
+    * ``drop_at_<step>`` — dropped at that emit step;
+    * ``tail_<n>`` — n equal bytes, n in 1..14;
+    * ``full_minus_1`` / ``full_exact`` — rung - 1 / rung mixed bytes.
+
+    Screen matcher (the serial model runs on them too)
+    * ``lane_0`` / ``lane_63`` — the hit lane of a full round;
+    * ``last_lane_mflimit`` — hit at p == mflimit, the last in-range
+      lane of a partial round;
+    * ``two_dry_then_hit``, ``two_hits`` (the first wins, lanes above it
+      do not insert), ``batch_blind`` (the only source lies in the same
+      round: the two policies differ), ``dry_exit`` (a dry round
+      carries pos past mflimit)."""
+    if rung in _MATCHER_CACHE:
+        return list(_MATCHER_CACHE[rung])
+    assert rung in MATCHER_RUNGS
+    seed = 0x3A7C0 ^ rung
+    out: List[Tuple[str, bytes]] = []
+
+    def add(name, build):
+        out.append((name, _pick(name, seed + len(out), build)))
+
+    if rung == 4096:
+        for a in range(4):
+            for b in range(4):
+                add("residue_%d%d" % (a, b), _residue_block(a, b))
+        for k in EXT_MISS_K:
+            add("ext_%d_miss" % k, _ext_miss_block(k))
+        for k in EXT_LIMIT_K:
+            add("ext_%d_limit" % k, _ext_limit_block(k, rung))
+        for period in PERIODS:
+            add("period_%d" % period, _period_block(period))
+        add("collide", _collide_block)
+        add("reprime_only", _reprime_block)
+        for name in ("fit_m1", "fit_0", "fit_p1"):
+            out.append((name, _pick(name, seed + len(out), _fit_block,
+                                    tries=4000)))
+        for n in range(1, 15):
+            out.append(("tail_%d" % n, b"\x07" * n))
+        add("lane_0", lambda rng: _repeat_block(rng, 8, 128,
+                                                rng.randbytes(12), 220))
+        add("lane_63", lambda rng: _repeat_block(rng, 8, 191,
+                                                 rng.randbytes(12)))
+        add("last_lane_mflimit", _last_lane_block(rung))
+        add("two_dry_then_hit", lambda rng: _repeat_block(
+            rng, 8, 133, rng.randbytes(12)))
+        add("two_hits", _two_hits_block)
+        add("batch_blind", _batch_blind_block)
+        add("dry_exit", _dry_exit_block(rung))
+    out.append(("zeros_full", b"\0" * rung))
+    for d in FAR_D:
+        add("far_%d" % d, _far_block(rung, d))
+    for step in DROP_STEPS:
+        if step != "mlen" or rung >= 8192:
+            add("drop_at_" + step, _drop_block(step, rung))
+    for name, n in (("full_minus_1", rung - 1), ("full_exact", rung)):
+        out.append((name, _pick_kept(seed + len(out), n)))
+    assert all(len(b) <= rung for _, b in out)
+    _MATCHER_CACHE[rung] = tuple(out)
+    return out
+
+
+def matcher_launch(rung: int) -> Tuple[List[str], List[bytes]]:
+    """-> (names, slots): the cases of one rung as the wrapper's single
+    launch sees them with ``block_raw = rung``.  Every block is
+    zero-padded to its slot except ``full_minus_1``, which goes last and
+    stays rung - 1 bytes: the launch's ragged final block."""
+    cases = matcher_blocks(rung)
+    cases = [c for c in cases if c[0] != "full_minus_1"] + \
+        [c for c in cases if c[0] == "full_minus_1"]
+    names = [c[0] for c in cases]
+    slots = [pad_slot(b, rung) for _, b in cases[:-1]] + [cases[-1][1]]
+    return names, slots
+
+
+SECOND_TRIP_GRID = 1 << 20     # grid cap in compress_blocks
+SECOND_TRIP_SOURCES = 61
+SECOND_TRIP_TOOBIG = (3, 17, 40, 63)
+
+
+def second_trip_launch():
+    """-> (buffer, src_off, src_len, n_blocks): 61 distinct source
+    blocks of 0..48 bytes at 16-byte-aligned offsets of one small
+    buffer, for one launch of ``(1 << 20) + 64`` blocks in which block i
+    reads source i % 61.  The grid is capped at 1 << 20 workgroups, so
+    workgroup w < 64 compresses blocks w and w + (1 << 20), and as 61 is
+    odd the two read different sources.  Lengths cover 0, 12, 13 and 48
+    bytes; sources 0..2 are 48 equal bytes, a 48-byte period-4 pattern
+    (both kept by the serial matcher) and 48 random bytes (dropped)."""
+    rng = random.Random(0x2D7219)
+    lens = [48, 48, 48, 0, 12, 13] + [
+        rng.randint(1, 48) for _ in range(SECOND_TRIP_SOURCES - 6)]
+    blocks = []
+    for i, n in enumerate(lens):
+        if i == 0:
+            b = b"\x11" * n
+        elif i == 1:
+            b = (b"shp4" * 12)[:n]
+        elif i % 3 == 2:
+            b = rng.randbytes(n)
+        elif i % 3 == 0:
+            b = bytes([rng.randrange(256)]) * n
+        else:
+            pat = rng.randbytes(rng.randint(1, 5))
+            b = (pat * 48)[:n]
+        blocks.append(b)
+    assert len(set(blocks)) == len(blocks) == SECOND_TRIP_SOURCES
+    buf = bytearray(SECOND_TRIP_SOURCES * 48)
+    offs = [48 * i for i in range(SECOND_TRIP_SOURCES)]
+    for off, b in zip(offs, blocks):
+        buf[off:off + len(b)] = b
+    return bytes(buf), offs, lens, SECOND_TRIP_GRID + 64
+
+
 # ---------------------------------------------------------- shard corpora
 SHARD_BLOCK_SIZES = (4096, 8192, 16384, 32768, 65536)
 # final-block variant -> True when the writer must store it

@@ -6,10 +6,13 @@ leaves open: grid-stride second trips, the multi-chain CRC
 instantiations, every LZ4 decoder geometry on both the single-wave and
 the producer/consumer kernel (with guard bytes around every output
 slot), the decoder's per-block error codes, the staged decoder path,
-the untested compressor instantiations and encoding edges, and SHA-256
+the untested compressor instantiations and encoding edges, both
+compressors against a Python model of their match policy, and SHA-256
 tail-page padding.  Every comparison is exact (bytes or integers)
-against gf2, lz4py or hashlib; inputs come from ops_edge_corpus.py and
-are seeded."""
+against gf2, lz4py, lz4_match_model or hashlib; inputs come from
+ops_edge_corpus.py and are seeded."""
+import ctypes
+import functools
 import hashlib
 import os
 import subprocess
@@ -22,6 +25,7 @@ torch = pytest.importorskip("torch")
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import lz4_match_model as match_model  # noqa: E402
 import ops_edge_corpus as corpus  # noqa: E402
 
 from shipyard_amd.data import lz4py  # noqa: E402
@@ -591,3 +595,157 @@ class TestGpuCompressorEdges:
             assert ops.lz4_all_ok(status), (name, status.cpu())
             corpus.check_slots(out.cpu().numpy(), slot,
                                [raws[b] for b in kept])
+
+
+# ------------------------------------------- GPU matchers against the model
+@functools.lru_cache(maxsize=None)
+def _model_stream(screen: bool, block: bytes):
+    fn = match_model.screen_model if screen else match_model.greedy_model
+    return fn(block)
+
+
+def _direct_compress(screen: bool, buf: bytes, in_off, in_len, stride: int,
+                     raw_cap: int):
+    """One launch through the C entry point with buffers of the test's
+    own: slots GUARD-filled, lengths pre-filled with 0xFFFFFFFF.
+    -> (slots as a numpy array, uint32 lengths)"""
+    from shipyard_amd import ops
+
+    lib = ops._load()
+    n_blocks = len(in_len)
+    d_data = _cuda(buf)
+    assert d_data.data_ptr() % 16 == 0
+    d_off = _cuda(np.asarray(in_off, dtype=np.uint64).view(np.int64))
+    d_len = _cuda(np.asarray(in_len, dtype=np.uint32).view(np.int32))
+    d_out = torch.full((n_blocks * stride,), corpus.GUARD,
+                       dtype=torch.uint8, device="cuda")
+    d_lens = torch.full((n_blocks,), -1, dtype=torch.int32, device="cuda")
+    fn = lib.sy_lz4_compress_blocks_gpu2 if screen \
+        else lib.sy_lz4_compress_blocks_gpu
+    rc = fn(ctypes.c_void_p(d_data.data_ptr()),
+            ctypes.c_void_p(d_off.data_ptr()),
+            ctypes.c_void_p(d_len.data_ptr()),
+            ctypes.c_void_p(d_out.data_ptr()), ctypes.c_uint64(stride),
+            ctypes.c_void_p(d_lens.data_ptr()), ctypes.c_uint32(n_blocks),
+            ctypes.c_uint32(raw_cap), ops._stream())
+    assert rc == 0
+    torch.cuda.synchronize()
+    return d_out.cpu().numpy(), d_lens.cpu().numpy().view(np.uint32)
+
+
+class TestGpuMatchersEqualModel:
+    """Both compressor kernels byte for byte against lz4_match_model on
+    the matcher corpus (pinned on the CPU by test_lz4_match_model.py)."""
+
+    def _wrapper_launch(self, rung: int, screen: bool):
+        names, slots = corpus.matcher_launch(rung)
+        blobs, _, _, lens = _gpu_compress(b"".join(slots), rung, screen)
+        want = [_model_stream(screen, s) for s in slots]
+        assert [int(x) for x in lens] == [len(w) if w else 0 for w in want], \
+            [n for n, x, w in zip(names, lens, want)
+             if int(x) != (len(w) if w else 0)]
+        assert blobs == want, [n for n, g, w in zip(names, blobs, want)
+                               if g != w]
+        return slots, want
+
+    @pytest.mark.parametrize("rung", corpus.MATCHER_RUNGS)
+    def test_serial_equals_model(self, rung):
+        """One wrapper launch per rung, a corpus block per slot
+        (zero-padded; the last block is rung - 1 bytes): lengths and
+        bytes of lz4_compress_kernel equal greedy_model, length 0
+        exactly where the model drops the block, and the CPU compressor
+        agrees."""
+        from shipyard_amd import ops
+
+        slots, want = self._wrapper_launch(rung, screen=False)
+        assert ops.lz4_compress_blocks(b"".join(slots), rung) == want
+
+    @pytest.mark.parametrize("rung", corpus.MATCHER_RUNGS)
+    def test_screen_equals_model(self, rung):
+        """The same launch on lz4_compress_screen_kernel against
+        screen_model: atomicMax makes its stream deterministic, so the
+        comparison is exact."""
+        self._wrapper_launch(rung, screen=True)
+
+    @pytest.mark.parametrize("screen", [False, True])
+    @pytest.mark.parametrize("rung", [4096, 65536])
+    def test_slots_and_lens_are_guarded(self, rung, screen):
+        """Direct launch with every corpus block at its own length (so
+        fit_*, drop_at_*, tail_* and full_minus_1 keep their feature)
+        and a 13-byte last block, in slots of rung + 64 bytes: every
+        length is written and equals the model's, kept slots hold the
+        model's stream, and no byte from in_len[b] to the stride (for a
+        kept block: from its length) has changed.  cap = n, so a
+        dropped block may have written below in_len[b] only."""
+        cases = corpus.matcher_blocks(rung) + [("last_13", b"\x07" * 13)]
+        stride = rung + corpus.SLOT_SLACK
+        buf = b"".join(corpus.pad_slot(b, rung) for _, b in cases)
+        in_len = [len(b) for _, b in cases]
+        got, lens = _direct_compress(
+            screen, buf, [i * rung for i in range(len(cases))], in_len,
+            stride, rung)
+        assert not (lens == 0xFFFFFFFF).any(), "a length was not written"
+        want = [_model_stream(screen, b) for _, b in cases]
+        assert [int(x) for x in lens] == [len(w) if w else 0 for w in want], \
+            [c[0] for c, x, w in zip(cases, lens, want)
+             if int(x) != (len(w) if w else 0)]
+        assert any(w is None for w in want) and any(want)
+        for i, ((name, block), w) in enumerate(zip(cases, want)):
+            slot = got[i * stride:(i + 1) * stride]
+            clean = len(block)
+            if w is not None:
+                assert bytes(slot[:len(w)].tobytes()) == w, name
+                clean = len(w)
+            assert (slot[clean:] == corpus.GUARD).all(), (
+                name, clean + int(np.nonzero(
+                    slot[clean:] != corpus.GUARD)[0][0]))
+
+    @pytest.mark.parametrize("screen", [False, True])
+    def test_workgroup_compresses_second_block(self, screen):
+        """(1 << 20) + 64 blocks on the 1 << 20-workgroup grid at the
+        4 KiB rung: workgroup w < 64 compresses blocks w and w + (1 <<
+        20) and reuses sbuf and the hash table.  Block i reads source
+        i % 61 of 61 small sources, so the two differ; a few of the
+        first 64 blocks claim 4097 bytes, the `n > RAWCAP` `continue`
+        in front of an ordinary second trip: length 0, slot untouched.
+        Lengths and the whole 64 MiB slot array are compared in one
+        vectorised step with the model on the 61 sources (bytes below
+        in_len of a dropped block excepted)."""
+        here = os.path.dirname(os.path.abspath(__file__))
+        with open(os.path.join(os.path.dirname(here), "shipyard_amd", "ops",
+                               "csrc", "lz4_compress_gpu.hip")) as f:
+            assert ("grid = n_blocks < (1u << 20) ? n_blocks : (1u << 20)"
+                    in f.read())
+        buf, offs, src_lens, n_blocks = corpus.second_trip_launch()
+        assert n_blocks > 1 << 20
+        n_src, stride = len(offs), 64
+        which = np.arange(n_blocks) % n_src
+        toobig = np.asarray(corpus.SECOND_TRIP_TOOBIG)
+        in_off = np.asarray(offs, dtype=np.uint64)[which]
+        in_len = np.asarray(src_lens, dtype=np.uint32)[which]
+        in_len[toobig] = 4097
+        got, lens = _direct_compress(screen, buf, in_off, in_len, stride,
+                                     4096)
+
+        streams = [_model_stream(screen, buf[o:o + n])
+                   for o, n in zip(offs, src_lens)]
+        if not screen:
+            assert any(streams) and not all(streams)
+        tile = np.full((n_src, stride), corpus.GUARD, dtype=np.uint8)
+        care = np.ones((n_src, stride), dtype=bool)
+        for i, (w, n) in enumerate(zip(streams, src_lens)):
+            if w is None:
+                care[i, :n] = False
+            else:
+                tile[i, :len(w)] = np.frombuffer(w, dtype=np.uint8)
+        want_lens = np.asarray([len(w) if w else 0 for w in streams],
+                               dtype=np.uint32)[which]
+        want_lens[toobig] = 0
+        bad = np.nonzero(lens != want_lens)[0]
+        assert bad.size == 0, (int(bad[0]), int(lens[bad[0]]))
+        want, care = tile[which], care[which]
+        want[toobig], care[toobig] = corpus.GUARD, True
+        wrong = np.nonzero(
+            ((got.reshape(n_blocks, stride) != want) & care).any(axis=1))[0]
+        assert wrong.size == 0, "first differing slot %d (source %d)" % (
+            wrong[0], wrong[0] % n_src)

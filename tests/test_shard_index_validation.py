@@ -520,6 +520,22 @@ class TestWrapperAlignment:
                 ops.lz4_compress_blocks_gpu(view, 4096, screen=screen)
         assert lib.launches == 0
 
+    @pytest.mark.parametrize("block_raw", [0, -4096, 1, 15, 17, 1000,
+                                           4095, 4104, 65535])
+    def test_lz4_compress_blocks_gpu_block_raw(self, lib, block_raw):
+        """Blocks are staged with uint4 loads from blk * block_raw: a
+        block_raw that is not a positive multiple of 16 (0 would also
+        divide by zero) is a ValueError before any launch, ahead of
+        the device assert."""
+        from shipyard_amd import ops
+
+        data = torch.zeros(65536, dtype=torch.uint8)
+        assert data.data_ptr() % 16 == 0
+        for screen in (False, True):
+            with pytest.raises(ValueError, match="multiple of 16"):
+                ops.lz4_compress_blocks_gpu(data, block_raw, screen=screen)
+        assert lib.launches == 0
+
     def test_lz4_decode_blocks_out_only(self, lib, view):
         from shipyard_amd import ops
 
