@@ -1106,35 +1106,19 @@ def _check_rows(lens, row_stride: int, fill: int) -> None:
             f"row_stride={row_stride}")
 
 
-def _decode_ranges(d_comp, idx: ShardIndex, sel, comp_off, offs, lens,
-                   device, verify: bool, row_stride: int, fill: int):
-    """The device side of a range read, shared by
-    ``decode_ranges_device`` and ``ShardStager.stage_ranges``: decode,
-    unfilter, verify, gather.  ``sel`` are the selected block ids and
-    ``comp_off`` where their payload starts in ``d_comp`` (the table's
-    column for a full payload, rebased offsets for a partial one);
-    ``offs``/``lens`` are checked numpy int64 arrays, the index is
-    validated and ``_check_rows`` has passed."""
+def _decode_selected(d_comp, idx: ShardIndex, sel, comp_off, offs, lens,
+                     device, verify: bool):
+    """The first half of a device range read, shared by the byte path
+    (``_decode_ranges``) and the typed path (``_decode_rows``): decode
+    the selected blocks ``sel`` (at least one) into a compact scratch
+    tensor, undo the filters, verify.  Returns the scratch and, as a
+    device int64 tensor, the byte offset in it of every range
+    (``_scratch_offsets``)."""
     import numpy as np
     import torch
 
     from shipyard_amd import ops
 
-    n = len(offs)
-    row_stride = int(row_stride)
-    if n == 0:
-        return torch.empty((0, row_stride) if row_stride else 0,
-                           dtype=torch.uint8, device=device)
-    if row_stride:
-        out = torch.full((n, row_stride), int(fill), dtype=torch.uint8,
-                         device=device)
-        dst_off = np.arange(n, dtype=np.int64) * row_stride
-    else:
-        out = torch.empty(int(lens.sum()), dtype=torch.uint8, device=device)
-        dst_off = np.zeros(n, dtype=np.int64)
-        np.cumsum(lens[:-1], out=dst_off[1:])
-    if not len(sel):
-        return out  # nothing but empty ranges
     block_raw = int(idx.block_raw)
     t = idx.table[sel]
     scratch = torch.empty(
@@ -1155,12 +1139,49 @@ def _decode_ranges(d_comp, idx: ShardIndex, sel, comp_off, offs, lens,
             bad = sel[(~eq).numpy()][:8].tolist()
             raise ValueError(f"GPU CRC mismatch in blocks {bad}")
     src_off = _scratch_offsets(offs, lens, sel, block_raw, idx.n_blocks)
+    return scratch, _to_device(src_off, device)
 
-    def to_dev(arr):
-        return torch.from_numpy(np.ascontiguousarray(arr)).to(device)
 
-    ops.gather_ranges(scratch, to_dev(src_off), to_dev(lens),
-                      out.view(-1), to_dev(dst_off))
+def _to_device(arr, device):
+    import numpy as np
+    import torch
+
+    return torch.from_numpy(np.ascontiguousarray(arr)).to(device)
+
+
+def _decode_ranges(d_comp, idx: ShardIndex, sel, comp_off, offs, lens,
+                   device, verify: bool, row_stride: int, fill: int):
+    """The device side of a range read, shared by
+    ``decode_ranges_device`` and ``ShardStager.stage_ranges``: decode,
+    unfilter, verify (``_decode_selected``), gather.  ``sel`` are the
+    selected block ids and ``comp_off`` where their payload starts in
+    ``d_comp`` (the table's column for a full payload, rebased offsets
+    for a partial one); ``offs``/``lens`` are checked numpy int64
+    arrays, the index is validated and ``_check_rows`` has passed."""
+    import numpy as np
+    import torch
+
+    from shipyard_amd import ops
+
+    n = len(offs)
+    row_stride = int(row_stride)
+    if n == 0:
+        return torch.empty((0, row_stride) if row_stride else 0,
+                           dtype=torch.uint8, device=device)
+    if row_stride:
+        out = torch.full((n, row_stride), int(fill), dtype=torch.uint8,
+                         device=device)
+        dst_off = np.arange(n, dtype=np.int64) * row_stride
+    else:
+        out = torch.empty(int(lens.sum()), dtype=torch.uint8, device=device)
+        dst_off = np.zeros(n, dtype=np.int64)
+        np.cumsum(lens[:-1], out=dst_off[1:])
+    if not len(sel):
+        return out  # nothing but empty ranges
+    scratch, src_off = _decode_selected(d_comp, idx, sel, comp_off, offs,
+                                        lens, device, verify)
+    ops.gather_ranges(scratch, src_off, _to_device(lens, device),
+                      out.view(-1), _to_device(dst_off, device))
     return out
 
 
@@ -1206,6 +1227,167 @@ def decode_ranges_device(d_comp, idx: ShardIndex, offs, lens, device,
     sel = _select_blocks(offs, lens, int(idx.block_raw), idx.n_blocks)
     return _decode_ranges(d_comp, idx, sel, idx.table["comp_off"][sel],
                           offs, lens, device, verify, row_stride, fill)
+
+
+# -------------------------------------------------------------- row reads
+def _row_types(src_dtype, out_dtype, pad):
+    """The type arguments of a row read: (source element bytes, numpy
+    source dtype, numpy output dtype, pad as an int).  ``out_dtype`` is
+    anything that names int32 or int64 (a numpy or torch dtype, a
+    string).  ValueError for an unknown type, a conversion that does not
+    keep every value (``u4`` into int32) and a pad outside
+    ``out_dtype``."""
+    import numpy as np
+
+    from shipyard_amd import ops
+
+    try:
+        out = np.dtype(out_dtype)
+    except TypeError:
+        try:  # torch.int32 and its like
+            out = np.dtype(str(out_dtype).rpartition(".")[2])
+        except TypeError:
+            out = None
+    if out not in (np.dtype(np.int32), np.dtype(np.int64)):
+        raise ValueError(
+            f"rows: out_dtype={out_dtype!r} must be int32 or int64")
+    size, signed = ops.widen_sizes(src_dtype, 8 * out.itemsize)
+    pad = ops.check_widen_pad(pad, 8 * out.itemsize)
+    return size, np.dtype(f"<{'i' if signed else 'u'}{size}"), out, pad
+
+
+def _as_rows(starts, counts, size: int, raw_size: int, row_elems: int):
+    """``starts``/``counts``, in elements of ``size`` bytes, as two
+    equally long 1-D numpy int64 arrays, checked against ``raw_size``
+    and ``row_elems``.  ValueError names the first bad row."""
+    import numpy as np
+
+    if int(row_elems) < 0:
+        raise ValueError(f"row_elems={row_elems} must not be negative")
+    starts = np.ascontiguousarray(starts, dtype=np.int64).reshape(-1)
+    counts = np.ascontiguousarray(counts, dtype=np.int64).reshape(-1)
+    if len(starts) != len(counts):
+        raise ValueError(
+            f"rows: {len(starts)} starts but {len(counts)} counts")
+    # (start + count) * size <= raw_size without a product or a sum that
+    # could wrap: count the elements that can be addressed
+    n_el = int(raw_size) // size
+    bad = (starts < 0) | (counts < 0) | (starts > n_el)
+    bad |= counts > n_el - np.minimum(starts, n_el)
+    if bad.any():
+        i = int(np.argmax(bad))
+        raise ValueError(
+            f"rows: row {i} (start {int(starts[i])}, count "
+            f"{int(counts[i])}) is negative or ends past the {n_el} "
+            f"elements of {size} bytes in raw_size={int(raw_size)}")
+    if len(counts) and int(counts.max()) > row_elems:
+        i = int(np.argmax(counts > row_elems))
+        raise ValueError(
+            f"rows: row {i} has {int(counts[i])} elements, more than "
+            f"row_elems={row_elems}")
+    return starts, counts
+
+
+def read_rows_cpu(buf: bytes, starts, counts, src_dtype, out_dtype,
+                  row_elems: int, pad: int, verify: bool = True):
+    """CPU reference of the row readers: a numpy ``[n, row_elems]``
+    array of ``out_dtype`` (int32 or int64) whose row ``i`` holds the
+    ``counts[i]`` elements of type ``src_dtype`` (``u1``, ``u2``,
+    ``i2``, ``u4``, ``i4``, little-endian) that start at element
+    ``starts[i]`` of the shard in ``buf``, followed by ``pad``.  All
+    units are elements of ``src_dtype``; bytes of ``raw_size`` behind
+    the last whole element cannot be addressed.  Built on
+    ``read_ranges_cpu`` (only touched blocks are decoded and verified)
+    and ``astype``.  Each bad argument is a ValueError, see
+    ``decode_rows_device``."""
+    import numpy as np
+
+    idx = read_index(buf)
+    size, src_np, out_np, pad = _row_types(src_dtype, out_dtype, pad)
+    starts, counts = _as_rows(starts, counts, size, idx.raw_size, row_elems)
+    data = read_ranges_cpu(buf, starts * size, counts * size, verify=verify)
+    out = np.full((len(starts), int(row_elems)), pad, dtype=out_np)
+    # the ranges come back concatenated in row order, as the mask walks
+    live = np.arange(int(row_elems))[None, :] < counts[:, None]
+    out[live] = np.frombuffer(data, dtype=src_np).astype(out_np)
+    return out
+
+
+def _decode_rows(d_comp, idx: ShardIndex, sel, comp_off, starts, counts,
+                 device, verify: bool, src_dtype, out_np, row_elems: int,
+                 pad: int):
+    """The device side of a row read, shared by ``decode_rows_device``
+    and ``ShardStager.stage_rows``: ``_decode_selected`` as for a range
+    read, then ``ops.gather_widen``.  ``starts``/``counts`` are checked
+    numpy int64 arrays in elements, the index is validated and
+    ``_row_types`` has passed."""
+    import numpy as np
+    import torch
+
+    from shipyard_amd import ops
+
+    n = len(starts)
+    out = torch.empty((n, int(row_elems)),
+                      dtype=getattr(torch, out_np.name), device=device)
+    if n == 0:
+        return out
+    size = ops.widen_sizes(src_dtype, 8 * out_np.itemsize)[0]
+    if len(sel):
+        scratch, src_off = _decode_selected(
+            d_comp, idx, sel, comp_off, starts * size, counts * size,
+            device, verify)
+    else:  # nothing but empty rows: nothing to decode, all of it pad
+        scratch = torch.empty(0, dtype=torch.uint8, device=device)
+        src_off = _to_device(np.zeros(n, dtype=np.int64), device)
+    ops.gather_widen(scratch, src_off, _to_device(counts, device), out,
+                     src_dtype, pad)
+    return out
+
+
+def decode_rows_device(d_comp, idx: ShardIndex, starts, counts, device,
+                       src_dtype, out_dtype, row_elems: int, pad: int,
+                       verify: bool = True):
+    """Typed random-access read of an uploaded shard payload in HBM: a
+    ``[n, row_elems]`` device tensor of ``out_dtype`` (int32 or int64)
+    whose row ``i`` holds the ``counts[i]`` elements of type
+    ``src_dtype`` (``u1``, ``u2``, ``i2``, ``u4``, ``i4``,
+    little-endian) that start at element ``starts[i]`` of the raw data,
+    zero- or sign-extended, followed by ``pad``: a batch for an
+    embedding lookup and a loss, padded with a token id or an
+    ``ignore_index``.  All units are elements of ``src_dtype``, which
+    keeps every row aligned to its element in the scratch (``block_raw``
+    is a multiple of 4096); a ``raw_size`` that is no multiple of the
+    element size is fine, its trailing bytes cannot be addressed.
+
+    Everything up to the last step is ``decode_ranges_device``'s: the
+    table is validated, the blocks that hold an element of a row are
+    selected, decoded into the compact scratch, unfiltered and, with
+    ``verify``, CRC-checked (only those blocks).  ``ops.gather_widen``
+    then writes the whole output in one launch: data widened, padding
+    filled, nothing pre-filled and no pass over the output afterwards.
+
+    Each of these is a ValueError raised before a tensor is made or a
+    kernel launched, naming the first bad row: unequal lengths of
+    ``starts`` and ``counts``, a negative value, a row that ends past
+    the last whole element of ``raw_size``, ``counts[i] > row_elems``,
+    ``row_elems < 0``, an unknown ``src_dtype`` or ``out_dtype``, a
+    conversion that does not keep every value (``u4`` into int32) and a
+    ``pad`` that ``out_dtype`` cannot hold.  No rows: an empty
+    ``[0, row_elems]`` tensor and no launch.  Rows that are all empty:
+    a tensor of ``pad``, written by the kernel, and nothing is decoded.
+
+    Peak HBM on top of the payload is that of ``decode_ranges_device``
+    with R = ``n * row_elems * out_dtype.itemsize`` and S selected
+    blocks: ``S * block_raw + R`` with no filter or delta alone,
+    ``2 * S * block_raw + R`` when shuffle or bitshuffle is on."""
+    validate_index(idx, d_comp.numel(), for_gpu=True)
+    size, _, out_np, pad = _row_types(src_dtype, out_dtype, pad)
+    starts, counts = _as_rows(starts, counts, size, idx.raw_size, row_elems)
+    sel = _select_blocks(starts * size, counts * size, int(idx.block_raw),
+                         idx.n_blocks)
+    return _decode_rows(d_comp, idx, sel, idx.table["comp_off"][sel],
+                        starts, counts, device, verify, src_dtype, out_np,
+                        row_elems, pad)
 
 
 def unpack_gpu(buf: bytes, device=None, verify: bool = True):

@@ -184,6 +184,51 @@ class ShardStager:
         ``StageResult.file_bytes`` counts the bytes actually read from
         the file (header + table + run spans) and ``raw_bytes`` is
         ``sum(lens)``.  A file that is not a SYSHARD is a ValueError."""
+
+        def plan(idx):
+            o, n = shardfmt._as_ranges(offs, lens, idx.raw_size)
+            shardfmt._check_rows(n, row_stride, fill)
+            return o, n, lambda d_payload, sel, comp_off: \
+                shardfmt._decode_ranges(
+                    d_payload, idx, sel, comp_off, o, n, self.device,
+                    self.verify, row_stride, fill)
+
+        return self._stage_selected(path, plan, "ranges")
+
+    def stage_rows(self, path, starts, counts, src_dtype, out_dtype,
+                   row_elems: int, pad: int) -> "tuple":
+        """Stage typed rows of one SYSHARD file into HBM: a
+        ``[n, row_elems]`` tensor of ``out_dtype`` (int32 or int64)
+        whose row ``i`` holds the ``counts[i]`` elements of type
+        ``src_dtype`` from element ``starts[i]`` of the raw data,
+        widened, followed by ``pad``.  Returns (tensor, StageResult);
+        the tensor is what ``shardfmt.decode_rows_device`` returns for
+        the same arguments, and the two share their code.
+
+        The file is read exactly as ``stage_ranges`` reads it: header,
+        table and the payload spans of the runs of selected blocks.
+        ``StageResult.file_bytes`` counts the bytes read and
+        ``raw_bytes`` the source bytes of the rows,
+        ``sum(counts)`` times the source element size."""
+
+        def plan(idx):
+            size, _, out_np, p = shardfmt._row_types(src_dtype, out_dtype,
+                                                     pad)
+            s, c = shardfmt._as_rows(starts, counts, size, idx.raw_size,
+                                     row_elems)
+            return s * size, c * size, lambda d_payload, sel, comp_off: \
+                shardfmt._decode_rows(
+                    d_payload, idx, sel, comp_off, s, c, self.device,
+                    self.verify, src_dtype, out_np, row_elems, p)
+
+        return self._stage_selected(path, plan, "rows")
+
+    def _stage_selected(self, path, plan, what: str) -> "tuple":
+        """The file side of ``stage_ranges`` and ``stage_rows``.
+        ``plan(idx)`` looks at the request once the table is validated:
+        it raises ValueError or returns the byte ranges the request
+        needs (offs, lens) and ``decode(d_payload, sel, comp_off)``,
+        which turns the uploaded run spans into the result."""
         import os
 
         import numpy as np
@@ -213,8 +258,7 @@ class ShardStager:
             # same order as decode_ranges_device: the table, the ranges,
             # and only then anything that reads, allocates or launches
             shardfmt.validate_index(idx, size - payload_off, for_gpu=True)
-            offs, lens = shardfmt._as_ranges(offs, lens, idx.raw_size)
-            shardfmt._check_rows(lens, row_stride, fill)
+            offs, lens, decode = plan(idx)
             sel = idx.select_blocks(offs, lens)
             comp_off = np.zeros(0, dtype=np.int64)
             d_payload = None
@@ -253,17 +297,15 @@ class ShardStager:
                 with torch.cuda.stream(self.stream):
                     d_payload = pin.to(self.device, non_blocking=True)
         with torch.cuda.stream(self.stream):
-            out = shardfmt._decode_ranges(
-                d_payload, idx, sel, comp_off, offs, lens, self.device,
-                self.verify, row_stride, fill)
+            out = decode(d_payload, sel, comp_off)
         self.stream.synchronize()
         sec = time.perf_counter() - t0
         file_bytes = payload_off + span_total
         res = StageResult(str(p), file_bytes, int(lens.sum()), sec,
                           decoded=True, verified=self.verify)
-        logger.info("staged %d ranges of %s: read %d of %d bytes, %d raw "
-                    "bytes in %.3fs", len(lens), p.name, file_bytes, size,
-                    res.raw_bytes, sec)
+        logger.info("staged %d %s of %s: read %d of %d bytes, %d raw "
+                    "bytes in %.3fs", len(lens), what, p.name, file_bytes,
+                    size, res.raw_bytes, sec)
         return out, res
 
     def _decode(self, d_payload, idx: shardfmt.ShardIndex):

@@ -130,6 +130,12 @@ def _load() -> ctypes.CDLL:
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
         ctypes.c_void_p,
     ]
+    lib.sy_gather_widen.restype = ctypes.c_int
+    lib.sy_gather_widen.argtypes = [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int,
+        ctypes.c_uint32, ctypes.c_int64, ctypes.c_void_p,
+    ]
     lib.sy_byte_shuffle.restype = ctypes.c_int
     lib.sy_byte_shuffle.argtypes = [
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32,
@@ -485,6 +491,136 @@ def gather_ranges(src, src_off, lens, dst, dst_off):
         ctypes.c_void_p(dst.data_ptr()), ctypes.c_void_p(dst_off.data_ptr()),
         ctypes.c_void_p(cum.data_ptr()), ctypes.c_uint32(n), _stream())
     _check(rc, "sy_gather_ranges")
+
+
+# source element types of gather_widen: name -> (bytes, signed), all
+# little-endian
+WIDEN_SRC_DTYPES = {"u1": (1, False), "u2": (2, False), "i2": (2, True),
+                    "u4": (4, False), "i4": (4, True)}
+# the kernel finds a lane's row with 32-bit arithmetic on column + 256
+WIDEN_MAX_ROW_ELEMS = (1 << 31) - 257
+
+
+def widen_sizes(src_dtype, dst_bits: int) -> tuple:
+    """(source element bytes, signed) of a ``gather_widen`` source type
+    for a destination of ``dst_bits`` (32 or 64) bit signed integers.
+    ValueError for an unknown type and for ``u4`` into 32 bits, the one
+    pair that cannot keep every value."""
+    if src_dtype not in WIDEN_SRC_DTYPES:
+        raise ValueError(
+            f"gather_widen: src_dtype={src_dtype!r} is not one of "
+            f"{sorted(WIDEN_SRC_DTYPES)}")
+    size, signed = WIDEN_SRC_DTYPES[src_dtype]
+    if 8 * size - signed > dst_bits - 1:
+        raise ValueError(
+            f"gather_widen: {src_dtype} does not fit int{dst_bits} (only "
+            "value-preserving conversions)")
+    return size, signed
+
+
+def check_widen_pad(pad, dst_bits: int) -> int:
+    """``pad`` as a Python int; ValueError unless it is an integer that
+    an int``dst_bits`` holds."""
+    import operator
+
+    try:
+        pad = operator.index(pad)
+    except TypeError:
+        raise ValueError(f"gather_widen: pad={pad!r} is not an integer")
+    if not -(1 << (dst_bits - 1)) <= pad < 1 << (dst_bits - 1):
+        raise ValueError(
+            f"gather_widen: pad={pad} does not fit int{dst_bits}")
+    return pad
+
+
+def gather_widen(src, src_off, counts, dst, src_dtype: str, pad: int):
+    """Typed row gather: for every row ``i`` of the ``[n, T]`` tensor
+    ``dst``, ``dst[i, :counts[i]]`` receives the ``counts[i]`` elements
+    of type ``src_dtype`` that start at byte ``src_off[i]`` of ``src``,
+    zero-extended (``u1``, ``u2``, ``u4``) or sign-extended (``i2``,
+    ``i4``), and ``dst[i, counts[i]:]`` receives ``pad``.
+
+    ``src`` is a contiguous uint8 CUDA tensor whose base pointer is a
+    multiple of the source element size S; ``src_off`` (int64, bytes,
+    multiples of S) and ``counts`` (int64, elements, 0..T) are 1-D
+    tensors of length n on its device; ``dst`` is a contiguous 2-D
+    ``torch.int32`` or ``torch.int64`` tensor, whose base may be any
+    multiple of its element size (a view at +4 or +8 inside an
+    allocation is fine).  Only value-preserving conversions: every type
+    into int64, all but ``u4`` into int32 (``i4`` is a copy).  Rows in
+    any order; source rows may overlap or repeat.
+
+    One launch (gather_widen.hip): every element of ``dst`` is written
+    exactly once, so the caller does not pre-fill it, no byte outside
+    ``dst`` is written, and only the bytes of the rows are loaded.
+
+    A ``src`` that is not contiguous uint8, a wrong dtype or device of
+    an index tensor or of ``dst``, tensors that are not on a GPU,
+    unequal lengths, ``n != dst.shape[0]``, an unknown or forbidden
+    conversion, a ``pad`` that ``dst.dtype`` cannot hold and a ``src``
+    base that is no multiple of S are each a ValueError raised before
+    any launch;
+    ``n == 0`` or ``T == 0`` is a no-op without a launch.
+
+    The caller guarantees, and nothing checks, that every row lies
+    inside ``src``, that ``0 <= counts[i] <= T`` and that ``dst`` does
+    not overlap ``src``: the numbers are on the device, and looking at
+    them here would cost a synchronise (``shardfmt.decode_rows_device``
+    checks its rows on the host, where they come from)."""
+    import torch
+
+    if src.dtype != torch.uint8 or not src.is_contiguous():
+        raise ValueError(
+            "gather_widen: src must be a contiguous uint8 tensor")
+    if dst.dtype not in (torch.int32, torch.int64):
+        raise ValueError(
+            f"gather_widen: dst must be int32 or int64, not {dst.dtype}")
+    if dst.dim() != 2 or not dst.is_contiguous():
+        raise ValueError("gather_widen: dst must be a contiguous [n, T] "
+                         "tensor")
+    dst_size = dst.element_size()
+    size, signed = widen_sizes(src_dtype, 8 * dst_size)
+    pad = check_widen_pad(pad, 8 * dst_size)
+    if src.data_ptr() % size:
+        raise ValueError(
+            f"gather_widen: src base pointer must be a multiple of the "
+            f"{size}-byte element (tensor storage offset "
+            f"{src.storage_offset()})")
+    for t, which in ((src_off, "src_off"), (counts, "counts")):
+        if t.dtype != torch.int64:
+            raise ValueError(
+                f"gather_widen: {which} must be int64, not {t.dtype}")
+        if t.dim() != 1 or not t.is_contiguous():
+            raise ValueError(
+                f"gather_widen: {which} must be a contiguous 1-D tensor")
+        if t.device != src.device:
+            raise ValueError(
+                f"gather_widen: {which} is on {t.device}, src on "
+                f"{src.device}")
+    n, row_elems = dst.shape
+    if src_off.numel() != counts.numel() or counts.numel() != n:
+        raise ValueError(
+            f"gather_widen: {src_off.numel()} source offsets and "
+            f"{counts.numel()} counts for {n} rows of dst")
+    if n >= 1 << 32 or row_elems > WIDEN_MAX_ROW_ELEMS:
+        raise ValueError(
+            "gather_widen: at most 2**32 - 1 rows of at most "
+            f"{WIDEN_MAX_ROW_ELEMS} elements")
+    if dst.device != src.device:
+        raise ValueError(
+            f"gather_widen: dst is on {dst.device}, src on {src.device}")
+    if not src.is_cuda:
+        raise ValueError(
+            f"gather_widen: src and dst are on {src.device}, not on a GPU")
+    if n == 0 or row_elems == 0:
+        return
+    rc = _load().sy_gather_widen(
+        ctypes.c_void_p(src.data_ptr()), ctypes.c_void_p(src_off.data_ptr()),
+        ctypes.c_void_p(counts.data_ptr()), ctypes.c_void_p(dst.data_ptr()),
+        ctypes.c_uint32(n), ctypes.c_uint32(row_elems),
+        ctypes.c_uint32(size), ctypes.c_int(int(signed)),
+        ctypes.c_uint32(dst_size), ctypes.c_int64(pad), _stream())
+    _check(rc, "sy_gather_widen")
 
 
 FILTER_ELEM_SIZES = (2, 4, 8)

@@ -20,7 +20,8 @@ ARCH = os.environ.get("SHIPYARD_GPU_ARCH", "gfx950")
 SOURCES = ["crc32c.hip", "lz4_decode.hip", "sha256.hip",
            "gather_copy.hip", "stager.cpp", "lz4_compress.cpp",
            "lz4_compress_gpu.hip", "byte_shuffle.hip",
-           "delta_filter.hip", "bit_shuffle.hip", "gather_ranges.hip"]
+           "delta_filter.hip", "bit_shuffle.hip", "gather_ranges.hip",
+           "gather_widen.hip"]
 HEADERS = ["common.h", "shuffle_tile.h"]
 
 
