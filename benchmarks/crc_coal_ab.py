@@ -51,9 +51,6 @@ def main():
     assert torch.cuda.is_available()
     check_correct()
     size = 1 << 30
-    import ctypes
-
-    lib = ops._load()
 
     def run_v2(data, chunk):
         n_chains = gf2.pick_crc_chains(chunk)
@@ -63,13 +60,8 @@ def main():
                           device="cuda")
 
         def f(d):
-            lib.sy_crc32c_chunks(
-                ctypes.c_void_p(d.data_ptr()), ctypes.c_uint64(size),
-                ctypes.c_uint32(chunk),
-                ctypes.c_void_p(mats.data_ptr()),
-                ctypes.c_void_p(out.data_ptr()),
-                ctypes.c_uint64(size // chunk),
-                ctypes.c_uint32(n_chains), ops._stream())
+            ops._call("sy_crc32c_chunks", d, size, chunk, mats, out,
+                      size // chunk, n_chains)
         return f
 
     def run_v3(data, chunk):
@@ -79,12 +71,8 @@ def main():
                           device="cuda")
 
         def f(d):
-            lib.sy_crc32c_chunks_coal(
-                ctypes.c_void_p(d.data_ptr()), ctypes.c_uint64(size),
-                ctypes.c_uint32(chunk),
-                ctypes.c_void_p(mats.data_ptr()),
-                ctypes.c_void_p(out.data_ptr()),
-                ctypes.c_uint64(size // chunk), ops._stream())
+            ops._call("sy_crc32c_chunks_coal", d, size, chunk, mats, out,
+                      size // chunk)
         return f
 
     for chunk in (65536, 262144, 1048576):

@@ -67,15 +67,9 @@ def bench_crc(size=1 << 30, chunk=256 * 1024):
 def bench_sha(size=1 << 30, page=4096):
     data = torch.randint(0, 256, (size,), dtype=torch.uint8, device="cuda")
     out = torch.empty((size // page, 32), dtype=torch.uint8, device="cuda")
-    import ctypes
-
-    lib = ops._load()
 
     def run():
-        lib.sy_sha256_pages(
-            ctypes.c_void_p(data.data_ptr()), ctypes.c_uint64(size),
-            ctypes.c_uint32(page), ctypes.c_void_p(out.data_ptr()),
-            ctypes.c_uint64(size // page), ops._stream())
+        ops._call("sy_sha256_pages", data, size, page, out, size // page)
 
     sec = timeit(run)
     import hashlib
@@ -119,23 +113,11 @@ def bench_lz4(total_raw=1 << 30, distinct=64, block_raw=8 * 1024, pc=False):
     d_out_off, d_out_len = t64(out_off), t32(out_len)
     d_out = torch.empty(total_raw, dtype=torch.uint8, device=dev)
     d_status = torch.empty(n_blocks, dtype=torch.uint32, device=dev)
-    import ctypes
-
-    lib = ops._load()
-
-    fn = lib.sy_lz4_decode_blocks_pc if pc else lib.sy_lz4_decode_blocks
+    entry = "sy_lz4_decode_blocks_pc" if pc else "sy_lz4_decode_blocks"
 
     def run():
-        fn(
-            ctypes.c_void_p(d_comp.data_ptr()),
-            ctypes.c_void_p(d_in_off.data_ptr()),
-            ctypes.c_void_p(d_in_len.data_ptr()),
-            ctypes.c_void_p(d_out.data_ptr()),
-            ctypes.c_void_p(d_out_off.data_ptr()),
-            ctypes.c_void_p(d_out_len.data_ptr()),
-            ctypes.c_void_p(d_status.data_ptr()),
-            ctypes.c_uint32(n_blocks), ctypes.c_uint32(block_raw),
-            ops._stream())
+        ops._call(entry, d_comp, d_in_off, d_in_len, d_out, d_out_off,
+                  d_out_len, d_status, n_blocks, block_raw)
 
     sec = timeit(run, warmup=1, iters=3)
     assert ops.lz4_all_ok(d_status)

@@ -10,7 +10,6 @@ worst case.  Reports throughput and ratio per block size.
 """
 from __future__ import annotations
 
-import ctypes
 import json
 import sys
 import time
@@ -68,19 +67,10 @@ def bench_block_size(data: bytes, block_raw: int, total_raw: int) -> dict:
     d_out_off, d_out_len = t64(out_off), t32(out_len)
     d_out = torch.empty(pos, dtype=torch.uint8, device=dev)
     d_status = torch.empty(n_blocks, dtype=torch.uint32, device=dev)
-    lib = ops._load()
 
     def run():
-        lib.sy_lz4_decode_blocks(
-            ctypes.c_void_p(d_comp.data_ptr()),
-            ctypes.c_void_p(d_in_off.data_ptr()),
-            ctypes.c_void_p(d_in_len.data_ptr()),
-            ctypes.c_void_p(d_out.data_ptr()),
-            ctypes.c_void_p(d_out_off.data_ptr()),
-            ctypes.c_void_p(d_out_len.data_ptr()),
-            ctypes.c_void_p(d_status.data_ptr()),
-            ctypes.c_uint32(n_blocks), ctypes.c_uint32(block_raw),
-            ops._stream())
+        ops._call("sy_lz4_decode_blocks", d_comp, d_in_off, d_in_len, d_out,
+                  d_out_off, d_out_len, d_status, n_blocks, block_raw)
 
     run()
     torch.cuda.synchronize()

@@ -89,8 +89,9 @@ WORSE bit-shuffled than byte-shuffled (docs/35-gpu-data-plane.md).
 Adding a filter: add a row to ``FILTERS`` at its place in the writer
 order (flag bit, element-size bits, whether the device op may run in
 place), a numpy body transform for ``_filter_blocks`` as its reference,
-an ``ops`` binding with the arguments of ``ops.byte_shuffle``, and the
-kernel behind it; then add the row's keyword to the writers' signatures
+the kernel, its entry point's row in ``ops.SIGNATURES`` (the filters
+share one prototype) and an ``ops`` wrapper with the arguments of
+``ops.byte_shuffle``; then add the row's keyword to the writers' signatures
 and to ``ShardIndex``.  Flags, header parsing, validation and the CPU
 and device chains in both directions all follow from the row.  A filter
 that transforms its elements in groups passes the group size to
@@ -109,7 +110,7 @@ from pathlib import Path
 from typing import Callable, List, Optional
 
 from shipyard_amd.data import lz4py
-from shipyard_amd.ops import gf2
+from shipyard_amd.ops import FILTER_ELEM_SIZES, gf2
 
 MAGIC = b"SYSHARD1"
 HEADER = struct.Struct("<8sIIQI")
@@ -127,7 +128,6 @@ DEFAULT_BLOCK_RAW = 8 * 1024
 GPU_BLOCK_ALIGN = 4096
 GPU_LZ4_BLOCK_MAX = 64 * 1024
 FLAG_LZ4 = 0x1
-FILTER_ELEM_SIZES = (2, 4, 8)
 
 
 def _filter_blocks(data, block_raw: int, elem_size: int, inverse: bool,
@@ -460,6 +460,17 @@ def _align16(n: int) -> int:
     return (n + 15) & ~15
 
 
+def _to_device(arr, device, view=None):
+    """A numpy column as a tensor on ``device``; ``view`` reinterprets
+    it (torch.from_numpy takes no unsigned type wider than a byte, so a
+    uint32 column travels as its int32 view)."""
+    import numpy as np
+    import torch
+
+    t = torch.from_numpy(np.ascontiguousarray(arr)).to(device)
+    return t if view is None else t.view(view)
+
+
 def _compress_span(args):
     """Worker: compress blocks [lo, hi) of a span of raw bytes."""
     span, block_raw, lo_off = args
@@ -519,9 +530,7 @@ def pack(data: bytes, block_raw: int = DEFAULT_BLOCK_RAW,
                      for i, c in enumerate(nat)]
         except Exception:
             comps = []
-    if comps:
-        pass
-    elif compress and data and workers is not None:
+    if not comps and compress and data and workers is not None:
         import concurrent.futures as _cf
         import os as _os
 
@@ -536,7 +545,7 @@ def pack(data: bytes, block_raw: int = DEFAULT_BLOCK_RAW,
             for _, blocks_out in sorted(
                     pool.map(_compress_span, spans)):
                 comps.extend(blocks_out)
-    else:
+    elif not comps:
         for boff in range(0, len(data), block_raw):
             raw = data[boff:boff + block_raw]
             comp = lz4py.compress_block(raw) if compress else raw
@@ -655,26 +664,23 @@ def pack_gpu(data, block_raw: int = DEFAULT_BLOCK_RAW,
     d_payload = torch.zeros(max(total, 1), dtype=torch.uint8,
                             device=t.device)  # zero pad bytes
 
-    def dev(arr, view):
-        return torch.from_numpy(np.ascontiguousarray(arr)).to(
-            t.device).view(view)
-
+    dev = t.device
     comp_idx = np.nonzero(~stored)[0]
     if len(comp_idx):
         ops.gather_copy(
             d_out,
-            dev((comp_idx.astype(np.uint64) * stride).view(np.int64),
-                torch.int64),
-            d_payload, dev(offs[comp_idx].view(np.int64), torch.int64),
-            dev(lens_np[comp_idx].view(np.int32), torch.uint32))
+            _to_device((comp_idx.astype(np.uint64) * stride).view(np.int64),
+                       dev),
+            d_payload, _to_device(offs[comp_idx].view(np.int64), dev),
+            _to_device(lens_np[comp_idx].view(np.int32), dev, torch.uint32))
     st_idx = np.nonzero(stored)[0]
     if len(st_idx):
         ops.gather_copy(
             t,
-            dev((st_idx.astype(np.uint64) * block_raw).view(np.int64),
-                torch.int64),
-            d_payload, dev(offs[st_idx].view(np.int64), torch.int64),
-            dev(raw_lens[st_idx].view(np.int32), torch.uint32))
+            _to_device((st_idx.astype(np.uint64) * block_raw).view(np.int64),
+                       dev),
+            d_payload, _to_device(offs[st_idx].view(np.int64), dev),
+            _to_device(raw_lens[st_idx].view(np.int32), dev, torch.uint32))
     # D2H straight into pinned memory; the final join is then the
     # ONLY host-side copy of the payload
     pout = torch.empty(max(total, 1), dtype=torch.uint8,
@@ -876,24 +882,27 @@ def _stored_contiguous(idx) -> bool:
     return bool((t["comp_off"] == acc).all())
 
 
-def _verify_crcs_device(out, idx, dev) -> None:
-    """GPU-side CRC compare: one kernel + one device equality, no
-    per-block python lists."""
+def _verify_crcs_device(t, block_raw: int, want_crc, ids=None) -> None:
+    """CRC32C of every ``block_raw`` chunk of the device tensor ``t``
+    (one kernel) against the numpy uint32 column ``want_crc``.
+    ValueError naming the first 8 bad chunks: their positions, or
+    ``ids[position]`` when the chunks are selected blocks of a shard."""
     import numpy as np
     import torch
 
     from shipyard_amd import ops
 
-    crcs = ops.crc32c_chunks(out[:idx.raw_size].contiguous(),
-                             chunk_size=idx.block_raw)
+    crcs = ops.crc32c_chunks(t, chunk_size=block_raw)
     # crc32c_chunks finishes the GF(2) combine on the host and returns
     # a CPU tensor; compare there (one vectorized op, no python lists)
     want = torch.from_numpy(
-        np.ascontiguousarray(idx.table["crc"]).view(np.int32).copy())
+        np.ascontiguousarray(want_crc).view(np.int32).copy())
     eq = crcs.view(torch.int32).cpu() == want
     if not bool(eq.all().item()):
-        bad = (~eq).nonzero().flatten()[:8].tolist()
-        raise ValueError(f"GPU CRC mismatch in blocks {bad}")
+        bad = np.flatnonzero(~eq.numpy())
+        if ids is not None:
+            bad = ids[bad]
+        raise ValueError(f"GPU CRC mismatch in blocks {bad[:8].tolist()}")
 
 
 def _launch_block_decode(d_comp, comp_off, comp_len, raw_len, out, out_off,
@@ -910,25 +919,20 @@ def _launch_block_decode(d_comp, comp_off, comp_len, raw_len, out, out_off,
     from shipyard_amd import ops
 
     stored = comp_len == raw_len
-
-    def to_dev(arr, dtype):
-        return torch.from_numpy(np.ascontiguousarray(arr)).to(dev).view(
-            dtype)
-
     if stored.any():
         ops.gather_copy(
-            d_comp, to_dev(comp_off[stored].astype(np.int64), torch.int64),
-            out, to_dev(out_off[stored], torch.int64),
-            to_dev(raw_len[stored].view(np.int32), torch.uint32))
+            d_comp, _to_device(comp_off[stored].astype(np.int64), dev),
+            out, _to_device(out_off[stored], dev),
+            _to_device(raw_len[stored].view(np.int32), dev, torch.uint32))
     lz4 = ~stored
     if lz4.any():
         status = ops.lz4_decode_blocks(
             d_comp,
-            to_dev(comp_off[lz4].astype(np.int64), torch.int64),
-            to_dev(comp_len[lz4].view(np.int32), torch.uint32),
+            _to_device(comp_off[lz4].astype(np.int64), dev),
+            _to_device(comp_len[lz4].view(np.int32), dev, torch.uint32),
             out,
-            to_dev(out_off[lz4], torch.int64),
-            to_dev(raw_len[lz4].view(np.int32), torch.uint32),
+            _to_device(out_off[lz4], dev),
+            _to_device(raw_len[lz4].view(np.int32), dev, torch.uint32),
             raw_cap=block_raw)
         if not ops.lz4_all_ok(status):
             raise ValueError(
@@ -981,7 +985,8 @@ def decode_device(d_comp, idx: ShardIndex, device, verify: bool = True):
         src, idx.block_raw, _filter_elems("shard index", vars(idx)),
         borrowed)
     if verify:
-        _verify_crcs_device(out, idx, device)
+        _verify_crcs_device(out[:idx.raw_size].contiguous(), idx.block_raw,
+                            idx.table["crc"])
     return out
 
 
@@ -1117,8 +1122,6 @@ def _decode_selected(d_comp, idx: ShardIndex, sel, comp_off, offs, lens,
     import numpy as np
     import torch
 
-    from shipyard_amd import ops
-
     block_raw = int(idx.block_raw)
     t = idx.table[sel]
     scratch = torch.empty(
@@ -1131,22 +1134,9 @@ def _decode_selected(d_comp, idx: ShardIndex, sel, comp_off, offs, lens,
         scratch, block_raw, _filter_elems("shard index", vars(idx)),
         borrowed=False)
     if verify:
-        crcs = ops.crc32c_chunks(scratch, chunk_size=block_raw)
-        want = torch.from_numpy(
-            np.ascontiguousarray(t["crc"]).view(np.int32).copy())
-        eq = crcs.view(torch.int32).cpu() == want
-        if not bool(eq.all().item()):
-            bad = sel[(~eq).numpy()][:8].tolist()
-            raise ValueError(f"GPU CRC mismatch in blocks {bad}")
+        _verify_crcs_device(scratch, block_raw, t["crc"], ids=sel)
     src_off = _scratch_offsets(offs, lens, sel, block_raw, idx.n_blocks)
     return scratch, _to_device(src_off, device)
-
-
-def _to_device(arr, device):
-    import numpy as np
-    import torch
-
-    return torch.from_numpy(np.ascontiguousarray(arr)).to(device)
 
 
 def _decode_ranges(d_comp, idx: ShardIndex, sel, comp_off, offs, lens,

@@ -109,6 +109,28 @@ class ShardStager:
         self.stream.synchronize()
         return dev_buf
 
+    @staticmethod
+    def _read_table(f, p, size: int):
+        """Read the SYSHARD header and block table from the start of the
+        open file ``f`` (``p``, ``size`` bytes long): (parsed header,
+        table bytes), with ``f`` left at the payload.  None for a file
+        that does not begin with the magic; ValueError for one cut
+        inside its header or table, or with a bad filter flag."""
+        head = f.read(shardfmt.HEADER.size)
+        if head[:8] != shardfmt.MAGIC:
+            return None
+        if len(head) < shardfmt.HEADER.size:
+            raise ValueError(f"{p}: truncated inside the SYSHARD header")
+        hdr = shardfmt.parse_header(head)
+        table_bytes = shardfmt.ENTRY.size * hdr.n_blocks
+        table = b""
+        if size - shardfmt.HEADER.size >= table_bytes:
+            table = f.read(table_bytes)
+        if len(table) != table_bytes:
+            raise ValueError(
+                f"{p}: truncated inside the SYSHARD block table")
+        return hdr, table
+
     def stage_file(self, path) -> "tuple":
         """Stage one file into HBM.  SYSHARD files decode+verify on the
         GPU; plain files upload as-is.  Returns (tensor, StageResult).
@@ -118,9 +140,8 @@ class ShardStager:
         size = p.stat().st_size
         t0 = time.perf_counter()
         with open(p, "rb") as f:
-            head = f.read(shardfmt.HEADER.size)
-            is_shard = head[:8] == shardfmt.MAGIC
-            if not is_shard:
+            shard = self._read_table(f, p, size)
+            if shard is None:
                 if self.native:
                     out = self._upload_native(p, 0, size)
                 else:
@@ -129,19 +150,7 @@ class ShardStager:
                 sec = time.perf_counter() - t0
                 return out, StageResult(str(p), size, size, sec,
                                         decoded=False, verified=False)
-            if len(head) < shardfmt.HEADER.size:
-                raise ValueError(
-                    f"{p}: truncated inside the SYSHARD header")
-            # ValueError for a filter flag with a bad element size
-            hdr = shardfmt.parse_header(head)
-            table_bytes = shardfmt.ENTRY.size * hdr.n_blocks
-            if size - shardfmt.HEADER.size < table_bytes:
-                raise ValueError(
-                    f"{p}: truncated inside the SYSHARD block table")
-            table = f.read(table_bytes)
-            if len(table) != table_bytes:
-                raise ValueError(
-                    f"{p}: truncated inside the SYSHARD block table")
+            hdr, table = shard
             payload_total = size - shardfmt.HEADER.size - len(table)
             if self.native:
                 d_payload = self._upload_native(p, f.tell(), payload_total)
@@ -238,22 +247,11 @@ class ShardStager:
         size = p.stat().st_size
         t0 = time.perf_counter()
         with open(p, "rb") as f:
-            head = f.read(shardfmt.HEADER.size)
-            if head[:8] != shardfmt.MAGIC:
+            shard = self._read_table(f, p, size)
+            if shard is None:
                 raise ValueError(f"{p}: not a SYSHARD file")
-            if len(head) < shardfmt.HEADER.size:
-                raise ValueError(
-                    f"{p}: truncated inside the SYSHARD header")
-            hdr = shardfmt.parse_header(head)
-            table_bytes = shardfmt.ENTRY.size * hdr.n_blocks
-            if size - shardfmt.HEADER.size < table_bytes:
-                raise ValueError(
-                    f"{p}: truncated inside the SYSHARD block table")
-            table = f.read(table_bytes)
-            if len(table) != table_bytes:
-                raise ValueError(
-                    f"{p}: truncated inside the SYSHARD block table")
-            payload_off = shardfmt.HEADER.size + table_bytes
+            hdr, table = shard
+            payload_off = shardfmt.HEADER.size + len(table)
             idx = shardfmt.index_from_table(hdr, table)
             # same order as decode_ranges_device: the table, the ranges,
             # and only then anything that reads, allocates or launches

@@ -65,6 +65,40 @@ def is_built() -> bool:
     return _LIB_PATH.exists()
 
 
+_P, _STR = ctypes.c_void_p, ctypes.c_char_p
+_U32, _U64 = ctypes.c_uint32, ctypes.c_uint64
+_INT, _I64 = ctypes.c_int, ctypes.c_int64
+
+_LZ4_DECODE = (_P, _P, _P, _P, _P, _P, _P, _U32, _U32, _P)
+_LZ4_COMPRESS_GPU = (_P, _P, _P, _P, _U64, _P, _U32, _U32, _P)
+_BLOCK_FILTER = (_P, _P, _U64, _U32, _U32, _INT, _P)
+
+# C entry point -> argument types, one row per ``SY_EXPORT int sy_*``
+# prototype in csrc/ (every one returns int; hipStream_t is a pointer).
+# _load() applies it, _call() relies on it to convert plain ints, and
+# tests/test_ops_bindings.py compares it with the prototypes.
+SIGNATURES = {
+    "sy_crc32c_chunks": (_P, _U64, _U32, _P, _P, _U64, _U32, _P),
+    "sy_crc32c_chunks_coal": (_P, _U64, _U32, _P, _P, _U64, _P),
+    "sy_sha256_pages": (_P, _U64, _U32, _P, _U64, _P),
+    "sy_lz4_decode_blocks": _LZ4_DECODE,
+    "sy_lz4_decode_blocks_pc": _LZ4_DECODE,
+    "sy_lz4_compress_blocks_gpu": _LZ4_COMPRESS_GPU,
+    "sy_lz4_compress_blocks_gpu2": _LZ4_COMPRESS_GPU,
+    "sy_lz4_compress_blocks": (_STR, _U64, _U32, _P, _U64, _P, _U32, _INT),
+    "sy_gather_copy": (_P, _P, _P, _P, _P, _U32, _P),
+    "sy_gather_range_pieces": (_P, _P, _P, _P, _U32, _P),
+    "sy_gather_ranges": (_P, _U64, _P, _P, _P, _P, _P, _U32, _P),
+    "sy_gather_widen": (_P, _P, _P, _P, _U32, _U32, _U32, _INT, _U32, _I64,
+                        _P),
+    "sy_byte_shuffle": _BLOCK_FILTER,
+    "sy_delta_filter": _BLOCK_FILTER,
+    "sy_bit_shuffle": _BLOCK_FILTER,
+    "sy_stage_file": (_STR, _P, _U64, _U64, _U64, _INT, _P,
+                      ctypes.POINTER(ctypes.c_double)),
+}
+
+
 def _load() -> ctypes.CDLL:
     global _lib
     if _lib is not None:
@@ -89,82 +123,10 @@ def _load() -> ctypes.CDLL:
     except Exception:
         pass  # CPU-only host: the CPU entry points need no runtime
     lib = ctypes.CDLL(str(_LIB_PATH))
-    lib.sy_crc32c_chunks.restype = ctypes.c_int
-    lib.sy_crc32c_chunks.argtypes = [
-        ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
-        ctypes.c_uint32, ctypes.c_void_p,
-    ]
-    lib.sy_crc32c_chunks_coal.restype = ctypes.c_int
-    lib.sy_crc32c_chunks_coal.argtypes = [
-        ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
-        ctypes.c_void_p,
-    ]
-    lib.sy_lz4_decode_blocks.restype = ctypes.c_int
-    lib.sy_lz4_decode_blocks.argtypes = [
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
-        ctypes.c_uint32, ctypes.c_void_p,
-    ]
-    lib.sy_sha256_pages.restype = ctypes.c_int
-    lib.sy_sha256_pages.argtypes = [
-        ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p,
-        ctypes.c_uint64, ctypes.c_void_p,
-    ]
-    lib.sy_lz4_decode_blocks_pc.restype = ctypes.c_int
-    lib.sy_lz4_decode_blocks_pc.argtypes = lib.sy_lz4_decode_blocks.argtypes
-    lib.sy_gather_copy.restype = ctypes.c_int
-    lib.sy_gather_copy.argtypes = [
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
-    ]
-    lib.sy_gather_range_pieces.restype = ctypes.c_int
-    lib.sy_gather_range_pieces.argtypes = [
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-        ctypes.c_uint32, ctypes.c_void_p,
-    ]
-    lib.sy_gather_ranges.restype = ctypes.c_int
-    lib.sy_gather_ranges.argtypes = [
-        ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
-        ctypes.c_void_p,
-    ]
-    lib.sy_gather_widen.restype = ctypes.c_int
-    lib.sy_gather_widen.argtypes = [
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-        ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int,
-        ctypes.c_uint32, ctypes.c_int64, ctypes.c_void_p,
-    ]
-    lib.sy_byte_shuffle.restype = ctypes.c_int
-    lib.sy_byte_shuffle.argtypes = [
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32,
-        ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p,
-    ]
-    lib.sy_delta_filter.restype = ctypes.c_int
-    lib.sy_delta_filter.argtypes = lib.sy_byte_shuffle.argtypes
-    lib.sy_bit_shuffle.restype = ctypes.c_int
-    lib.sy_bit_shuffle.argtypes = lib.sy_byte_shuffle.argtypes
-    lib.sy_lz4_compress_blocks_gpu.restype = ctypes.c_int
-    lib.sy_lz4_compress_blocks_gpu.argtypes = [
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
-        ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
-    ]
-    lib.sy_lz4_compress_blocks_gpu2.restype = ctypes.c_int
-    lib.sy_lz4_compress_blocks_gpu2.argtypes = \
-        lib.sy_lz4_compress_blocks_gpu.argtypes
-    lib.sy_lz4_compress_blocks.restype = ctypes.c_int
-    lib.sy_lz4_compress_blocks.argtypes = [
-        ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p,
-        ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int,
-    ]
-    lib.sy_stage_file.restype = ctypes.c_int
-    lib.sy_stage_file.argtypes = [
-        ctypes.c_char_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64,
-        ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p,
-        ctypes.POINTER(ctypes.c_double),
-    ]
+    for entry, argtypes in SIGNATURES.items():
+        fn = getattr(lib, entry)
+        fn.restype = ctypes.c_int
+        fn.argtypes = list(argtypes)
     _lib = lib
     return lib
 
@@ -180,6 +142,62 @@ def _check(rc: int, what: str) -> None:
         raise RuntimeError(f"{what} failed with code {rc}")
 
 
+def _call(entry: str, *args, stream: bool = True) -> int:
+    """Call the C entry point ``entry`` of the library ``_load()`` gives
+    at this moment.  A tensor (anything with ``data_ptr()``) and a numpy
+    array go as the address of their first byte; a pointer plus an
+    offset is passed as an explicit ``ctypes.c_void_p``; ints and bytes
+    are left to the entry point's ``argtypes``.  With ``stream`` the
+    current torch stream is appended as the last argument.  RuntimeError
+    naming ``entry`` for a non-zero return code; returns it (0)
+    otherwise."""
+    fn = getattr(_load(), entry)
+    conv = []
+    for a in args:
+        if type(a) is not int:  # this runs once per launch: ints are cheap
+            data_ptr = getattr(a, "data_ptr", None)
+            if data_ptr is not None:
+                a = _P(data_ptr())
+            elif hasattr(a, "ctypes"):
+                a = _P(a.ctypes.data)
+        conv.append(a)
+    if stream:
+        conv.append(_stream())
+    rc = fn(*conv)
+    _check(rc, entry)
+    return rc
+
+
+def _check_aligned16(t, what: str, where: str = "", advice: str = "") -> None:
+    """ValueError unless the base pointer of tensor ``t``, which the
+    message calls ``what``, is a multiple of 16 (the kernels walk it
+    with uint4 accesses)."""
+    if t.data_ptr() % 16:
+        raise ValueError(
+            f"{what} base pointer must be 16-byte aligned{where} (tensor "
+            f"storage offset {t.storage_offset()}){advice}")
+
+
+_CLONE_IT = "; pass an aligned view or .clone() it"
+
+
+def _check_index_tensors(op: str, src, named) -> None:
+    """The index tensors of a gather, ``named`` as (tensor, name) pairs:
+    each int64, contiguous 1-D and on ``src``'s device, or ValueError in
+    ``op``'s name."""
+    import torch
+
+    for t, which in named:
+        if t.dtype != torch.int64:
+            raise ValueError(f"{op}: {which} must be int64, not {t.dtype}")
+        if t.dim() != 1 or not t.is_contiguous():
+            raise ValueError(
+                f"{op}: {which} must be a contiguous 1-D tensor")
+        if t.device != src.device:
+            raise ValueError(
+                f"{op}: {which} is on {t.device}, src on {src.device}")
+
+
 def _check_u8_device(t, what: str) -> None:
     """Input contract of the kernels that walk a tensor with uint4
     accesses from its base: uint8, contiguous, CUDA, and a base pointer
@@ -191,11 +209,7 @@ def _check_u8_device(t, what: str) -> None:
     import torch
 
     assert t.dtype == torch.uint8 and t.is_contiguous(), what
-    if t.data_ptr() % 16:
-        raise ValueError(
-            f"{what}: base pointer must be 16-byte aligned (tensor "
-            f"storage offset {t.storage_offset()}); pass an aligned "
-            "view or .clone() it")
+    _check_aligned16(t, f"{what}:", advice=_CLONE_IT)
     assert t.is_cuda, what
 
 
@@ -209,21 +223,14 @@ def crc32c_chunks_coal_raw(data, chunk_size: int = 256 * 1024):
     import torch
 
     _check_u8_device(data, "crc32c_chunks_coal_raw")
-    lib = _load()
     n = data.numel()
     if chunk_size % 32768 or n % chunk_size:
         raise ValueError("coalesced CRC needs chunk%32768==0 and "
                          "full chunks")
     n_chunks = n // chunk_size
-    mats = torch.tensor(gf2.coalesced_matrices(), dtype=torch.int64)
-    d_mats = mats.to(torch.uint32).to(data.device)
     out = torch.empty(n_chunks, dtype=torch.uint32, device=data.device)
-    rc = lib.sy_crc32c_chunks_coal(
-        ctypes.c_void_p(data.data_ptr()), ctypes.c_uint64(n),
-        ctypes.c_uint32(chunk_size), ctypes.c_void_p(d_mats.data_ptr()),
-        ctypes.c_void_p(out.data_ptr()), ctypes.c_uint64(n_chunks),
-        _stream())
-    _check(rc, "sy_crc32c_chunks_coal")
+    _call("sy_crc32c_chunks_coal", data, n, chunk_size,
+          _cached_mats("coal", chunk_size, data.device), out, n_chunks)
     return out.cpu()
 
 
@@ -241,7 +248,6 @@ def crc32c_chunks(data, chunk_size: int = 256 * 1024, finish: bool = True):
     import torch
 
     _check_u8_device(data, "crc32c_chunks")
-    lib = _load()
     n = data.numel()
     n_chunks = (n + chunk_size - 1) // chunk_size
     out = torch.empty(n_chunks, dtype=torch.uint32, device=data.device)
@@ -253,35 +259,21 @@ def crc32c_chunks(data, chunk_size: int = 256 * 1024, finish: bool = True):
     use_v3 = chunk_size % 32768 == 0 and n_full > 0 and \
         os.environ.get("SHIPYARD_CRC_V3", "1") != "0"
     if use_v3:
-        cmats = _cached_mats("coal", chunk_size, data.device)
-        rc = lib.sy_crc32c_chunks_coal(
-            ctypes.c_void_p(data.data_ptr()),
-            ctypes.c_uint64(n_full * chunk_size),
-            ctypes.c_uint32(chunk_size),
-            ctypes.c_void_p(cmats.data_ptr()),
-            ctypes.c_void_p(out.data_ptr()),
-            ctypes.c_uint64(n_full), _stream())
-        _check(rc, "sy_crc32c_chunks_coal")
+        _call("sy_crc32c_chunks_coal", data, n_full * chunk_size, chunk_size,
+              _cached_mats("coal", chunk_size, data.device), out, n_full)
     if not use_v3 or n_chunks > n_full:
         start = n_full if use_v3 else 0
-        sub_n = n - start * chunk_size
-        sub_chunks = n_chunks - start
         # resolved once: the cached operators and the launch agree
         n_chains = gf2.pick_crc_chains(chunk_size)
-        d_mats = _cached_mats("v2", chunk_size, data.device, n_chains)
-        rc = lib.sy_crc32c_chunks(
-            ctypes.c_void_p(data.data_ptr() + start * chunk_size),
-            ctypes.c_uint64(sub_n),
-            ctypes.c_uint32(chunk_size),
-            ctypes.c_void_p(d_mats.data_ptr()),
-            ctypes.c_void_p(out.data_ptr() + start * 4),
-            ctypes.c_uint64(sub_chunks),
-            ctypes.c_uint32(n_chains), _stream())
-        _check(rc, "sy_crc32c_chunks")
+        _call("sy_crc32c_chunks",
+              ctypes.c_void_p(data.data_ptr() + start * chunk_size),
+              n - start * chunk_size, chunk_size,
+              _cached_mats("v2", chunk_size, data.device, n_chains),
+              ctypes.c_void_p(out.data_ptr() + start * 4),
+              n_chunks - start, n_chains)
     raw = out.cpu()
     if not finish:
         return raw
-    fin = torch.empty_like(raw)
     full = gf2.matvec(list(gf2.zero_shift_operator(chunk_size)), 0xFFFFFFFF)
     tail_len = n - (n_chunks - 1) * chunk_size
     tail = gf2.matvec(list(gf2.zero_shift_operator(tail_len)), 0xFFFFFFFF)
@@ -297,8 +289,6 @@ def crc32c_chunks(data, chunk_size: int = 256 * 1024, finish: bool = True):
 
 def crc32c_file_digest(data, chunk_size: int = 256 * 1024) -> int:
     """Whole-buffer CRC32C via GPU chunk CRCs + host GF(2) combine."""
-    import torch
-
     raw = crc32c_chunks(data, chunk_size, finish=False).numpy()
     n = data.numel()
     acc = 0
@@ -341,7 +331,6 @@ def lz4_compress_blocks_gpu(data, block_raw: int,
             f"lz4_compress_blocks_gpu: block_raw must be a positive "
             f"multiple of 16 (uint4 staging loads), got {block_raw}")
     _check_u8_device(data, "lz4_compress_blocks_gpu")
-    lib = _load()
     n = data.numel()
     n_blocks = (n + block_raw - 1) // block_raw
     if n_blocks == 0:
@@ -359,16 +348,9 @@ def lz4_compress_blocks_gpu(data, block_raw: int,
                         device=data.device)
     d_lens = torch.zeros(n_blocks, dtype=torch.int32,
                          device=data.device)
-    fn = lib.sy_lz4_compress_blocks_gpu2 if screen \
-        else lib.sy_lz4_compress_blocks_gpu
-    rc = fn(
-        ctypes.c_void_p(data.data_ptr()),
-        ctypes.c_void_p(d_off.data_ptr()),
-        ctypes.c_void_p(d_len.data_ptr()),
-        ctypes.c_void_p(d_out.data_ptr()), ctypes.c_uint64(stride),
-        ctypes.c_void_p(d_lens.data_ptr()), ctypes.c_uint32(n_blocks),
-        ctypes.c_uint32(block_raw), _stream())
-    _check(rc, "sy_lz4_compress_blocks_gpu")
+    _call("sy_lz4_compress_blocks_gpu2" if screen
+          else "sy_lz4_compress_blocks_gpu",
+          data, d_off, d_len, d_out, stride, d_lens, n_blocks, block_raw)
     return d_out, stride, d_lens.cpu()
 
 
@@ -380,20 +362,14 @@ def lz4_compress_blocks(data: bytes, block_raw: int,
     Host-only — needs no GPU, just the built library."""
     import numpy as np
 
-    lib = _load()
     n_blocks = (len(data) + block_raw - 1) // block_raw
     if n_blocks == 0:
         return []
     stride = block_raw + block_raw // 255 + 32
     dst = np.empty(n_blocks * stride, dtype=np.uint8)
     lens = np.zeros(n_blocks, dtype=np.uint32)
-    rc = lib.sy_lz4_compress_blocks(
-        ctypes.c_char_p(data), ctypes.c_uint64(len(data)),
-        ctypes.c_uint32(block_raw),
-        ctypes.c_void_p(dst.ctypes.data), ctypes.c_uint64(stride),
-        ctypes.c_void_p(lens.ctypes.data), ctypes.c_uint32(n_blocks),
-        ctypes.c_int(threads))
-    _check(rc, "sy_lz4_compress_blocks")
+    _call("sy_lz4_compress_blocks", data, len(data), block_raw, dst, stride,
+          lens, n_blocks, threads, stream=False)
     out = []
     for b in range(n_blocks):
         ln = int(lens[b])
@@ -413,17 +389,10 @@ def gather_copy(src, src_off, dst, dst_off, lens):
     """Batched device gather-copy (stored shard blocks): one workgroup
     per block, uint4 body + byte tail.  src_off/dst_off int64 byte
     offsets (src 16 B aligned by the format), lens uint32."""
-    lib = _load()
     n = src_off.numel()
     if n == 0:
         return
-    rc = lib.sy_gather_copy(
-        ctypes.c_void_p(src.data_ptr()),
-        ctypes.c_void_p(src_off.data_ptr()),
-        ctypes.c_void_p(dst.data_ptr()),
-        ctypes.c_void_p(dst_off.data_ptr()),
-        ctypes.c_void_p(lens.data_ptr()), ctypes.c_uint32(n), _stream())
-    _check(rc, "sy_gather_copy")
+    _call("sy_gather_copy", src, src_off, dst, dst_off, lens, n)
 
 
 def gather_ranges(src, src_off, lens, dst, dst_off):
@@ -454,18 +423,8 @@ def gather_ranges(src, src_off, lens, dst, dst_off):
     for t, which in ((src, "src"), (dst, "dst")):
         assert t.dtype == torch.uint8 and t.is_contiguous(), \
             f"gather_ranges: {which}"
-    for t, which in ((src_off, "src_off"), (lens, "lens"),
-                     (dst_off, "dst_off")):
-        if t.dtype != torch.int64:
-            raise ValueError(
-                f"gather_ranges: {which} must be int64, not {t.dtype}")
-        if t.dim() != 1 or not t.is_contiguous():
-            raise ValueError(
-                f"gather_ranges: {which} must be a contiguous 1-D tensor")
-        if t.device != src.device:
-            raise ValueError(
-                f"gather_ranges: {which} is on {t.device}, src on "
-                f"{src.device}")
+    _check_index_tensors("gather_ranges", src, (
+        (src_off, "src_off"), (lens, "lens"), (dst_off, "dst_off")))
     n = lens.numel()
     if src_off.numel() != n or dst_off.numel() != n:
         raise ValueError(
@@ -477,20 +436,11 @@ def gather_ranges(src, src_off, lens, dst, dst_off):
         "gather_ranges: CUDA tensors on one device"
     if n == 0:
         return
-    lib = _load()
     pieces = torch.empty(n, dtype=torch.int64, device=src.device)
-    rc = lib.sy_gather_range_pieces(
-        ctypes.c_void_p(dst.data_ptr()), ctypes.c_void_p(dst_off.data_ptr()),
-        ctypes.c_void_p(lens.data_ptr()), ctypes.c_void_p(pieces.data_ptr()),
-        ctypes.c_uint32(n), _stream())
-    _check(rc, "sy_gather_range_pieces")
+    _call("sy_gather_range_pieces", dst, dst_off, lens, pieces, n)
     cum = torch.cumsum(pieces, 0)
-    rc = lib.sy_gather_ranges(
-        ctypes.c_void_p(src.data_ptr()), ctypes.c_uint64(src.numel()),
-        ctypes.c_void_p(src_off.data_ptr()), ctypes.c_void_p(lens.data_ptr()),
-        ctypes.c_void_p(dst.data_ptr()), ctypes.c_void_p(dst_off.data_ptr()),
-        ctypes.c_void_p(cum.data_ptr()), ctypes.c_uint32(n), _stream())
-    _check(rc, "sy_gather_ranges")
+    _call("sy_gather_ranges", src, src.numel(), src_off, lens, dst, dst_off,
+          cum, n)
 
 
 # source element types of gather_widen: name -> (bytes, signed), all
@@ -586,17 +536,8 @@ def gather_widen(src, src_off, counts, dst, src_dtype: str, pad: int):
             f"gather_widen: src base pointer must be a multiple of the "
             f"{size}-byte element (tensor storage offset "
             f"{src.storage_offset()})")
-    for t, which in ((src_off, "src_off"), (counts, "counts")):
-        if t.dtype != torch.int64:
-            raise ValueError(
-                f"gather_widen: {which} must be int64, not {t.dtype}")
-        if t.dim() != 1 or not t.is_contiguous():
-            raise ValueError(
-                f"gather_widen: {which} must be a contiguous 1-D tensor")
-        if t.device != src.device:
-            raise ValueError(
-                f"gather_widen: {which} is on {t.device}, src on "
-                f"{src.device}")
+    _check_index_tensors("gather_widen", src, (
+        (src_off, "src_off"), (counts, "counts")))
     n, row_elems = dst.shape
     if src_off.numel() != counts.numel() or counts.numel() != n:
         raise ValueError(
@@ -614,13 +555,8 @@ def gather_widen(src, src_off, counts, dst, src_dtype: str, pad: int):
             f"gather_widen: src and dst are on {src.device}, not on a GPU")
     if n == 0 or row_elems == 0:
         return
-    rc = _load().sy_gather_widen(
-        ctypes.c_void_p(src.data_ptr()), ctypes.c_void_p(src_off.data_ptr()),
-        ctypes.c_void_p(counts.data_ptr()), ctypes.c_void_p(dst.data_ptr()),
-        ctypes.c_uint32(n), ctypes.c_uint32(row_elems),
-        ctypes.c_uint32(size), ctypes.c_int(int(signed)),
-        ctypes.c_uint32(dst_size), ctypes.c_int64(pad), _stream())
-    _check(rc, "sy_gather_widen")
+    _call("sy_gather_widen", src, src_off, counts, dst, n, row_elems, size,
+          int(signed), dst_size, pad)
 
 
 FILTER_ELEM_SIZES = (2, 4, 8)
@@ -638,11 +574,7 @@ def _block_filter(name: str, entry: str, allow_in_place: bool, src, dst,
     for t, which in ((src, "src"), (dst, "dst")):
         assert t.dtype == torch.uint8 and t.is_contiguous(), \
             f"{name}: {which}"
-        if t.data_ptr() % 16:
-            raise ValueError(
-                f"{name}: {which} base pointer must be 16-byte "
-                f"aligned (tensor storage offset {t.storage_offset()}); "
-                "pass an aligned view or .clone() it")
+        _check_aligned16(t, f"{name}: {which}", advice=_CLONE_IT)
     n = src.numel()
     if dst.numel() != n:
         raise ValueError(f"{name}: src has {n} bytes but dst {dst.numel()}")
@@ -664,12 +596,7 @@ def _block_filter(name: str, entry: str, allow_in_place: bool, src, dst,
         f"{name}: CUDA tensors on one device"
     if n == 0:
         return
-    rc = getattr(_load(), entry)(
-        ctypes.c_void_p(src.data_ptr()), ctypes.c_void_p(dst.data_ptr()),
-        ctypes.c_uint64(n), ctypes.c_uint32(block_raw),
-        ctypes.c_uint32(elem_size), ctypes.c_int(int(bool(inverse))),
-        _stream())
-    _check(rc, entry)
+    _call(entry, src, dst, n, block_raw, elem_size, int(bool(inverse)))
 
 
 def byte_shuffle(src, dst, block_raw: int, elem_size: int,
@@ -781,29 +708,18 @@ def lz4_decode_blocks(comp, in_off, in_len, out, out_off, out_len,
     """
     import torch
 
-    if out.data_ptr() % 16:
-        raise ValueError(
-            "lz4_decode_blocks: out base pointer must be 16-byte "
-            f"aligned (tensor storage offset {out.storage_offset()})")
+    _check_aligned16(out, "lz4_decode_blocks: out")
     if pc is None:
         pc = os.environ.get("SHIPYARD_LZ4_PC", "0") == "1"
-    if comp.data_ptr() % 16 and (pc or _lz4_staged_by_env()):
-        raise ValueError(
-            "lz4_decode_blocks: comp base pointer must be 16-byte "
-            "aligned on the producer/consumer and staged paths (tensor "
-            f"storage offset {comp.storage_offset()})")
-    lib = _load()
-    entry = "sy_lz4_decode_blocks_pc" if pc else "sy_lz4_decode_blocks"
-    fn = getattr(lib, entry)
+    if pc or _lz4_staged_by_env():
+        _check_aligned16(
+            comp, "lz4_decode_blocks: comp",
+            where=" on the producer/consumer and staged paths")
     n_blocks = in_off.numel()
     status = torch.empty(n_blocks, dtype=torch.uint32, device=comp.device)
-    rc = fn(
-        ctypes.c_void_p(comp.data_ptr()), ctypes.c_void_p(in_off.data_ptr()),
-        ctypes.c_void_p(in_len.data_ptr()), ctypes.c_void_p(out.data_ptr()),
-        ctypes.c_void_p(out_off.data_ptr()), ctypes.c_void_p(out_len.data_ptr()),
-        ctypes.c_void_p(status.data_ptr()), ctypes.c_uint32(n_blocks),
-        ctypes.c_uint32(raw_cap), _stream())
-    _check(rc, entry)
+    _call("sy_lz4_decode_blocks_pc" if pc else "sy_lz4_decode_blocks",
+          comp, in_off, in_len, out, out_off, out_len, status, n_blocks,
+          raw_cap)
     return status
 
 
@@ -824,15 +740,10 @@ def sha256_pages(data, page_size: int = 4096):
     import torch
 
     _check_u8_device(data, "sha256_pages")
-    lib = _load()
     n = data.numel()
     n_pages = (n + page_size - 1) // page_size
     out = torch.empty((n_pages, 32), dtype=torch.uint8, device=data.device)
-    rc = lib.sy_sha256_pages(
-        ctypes.c_void_p(data.data_ptr()), ctypes.c_uint64(n),
-        ctypes.c_uint32(page_size), ctypes.c_void_p(out.data_ptr()),
-        ctypes.c_uint64(n_pages), _stream())
-    _check(rc, "sy_sha256_pages")
+    _call("sy_sha256_pages", data, n, page_size, out, n_pages)
     return out
 
 
@@ -847,11 +758,10 @@ def stage_file_native(path, dst, file_off: int = 0,
         n_bytes = os.path.getsize(path) - file_off
     assert dst.numel() >= n_bytes
     secs = ctypes.c_double(0.0)
+    # its own error text, and the stream is not the last argument
     rc = lib.sy_stage_file(
-        str(path).encode(), ctypes.c_void_p(dst.data_ptr()),
-        ctypes.c_uint64(file_off), ctypes.c_uint64(n_bytes),
-        ctypes.c_uint64(staging_mb << 20), ctypes.c_int(int(use_direct)),
-        _stream(), ctypes.byref(secs))
+        str(path).encode(), dst.data_ptr(), file_off, n_bytes,
+        staging_mb << 20, int(use_direct), _stream(), ctypes.byref(secs))
     if rc != 0:
         raise RuntimeError(f"sy_stage_file failed rc={rc} "
                            f"({os.strerror(-rc) if rc < 0 else 'hip'})")

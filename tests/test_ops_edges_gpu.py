@@ -11,7 +11,6 @@ compressors against a Python model of their match policy, and SHA-256
 tail-page padding.  Every comparison is exact (bytes or integers)
 against gf2, lz4py, lz4_match_model or hashlib; inputs come from
 ops_edge_corpus.py and are seeded."""
-import ctypes
 import functools
 import hashlib
 import os
@@ -611,7 +610,6 @@ def _direct_compress(screen: bool, buf: bytes, in_off, in_len, stride: int,
     -> (slots as a numpy array, uint32 lengths)"""
     from shipyard_amd import ops
 
-    lib = ops._load()
     n_blocks = len(in_len)
     d_data = _cuda(buf)
     assert d_data.data_ptr() % 16 == 0
@@ -620,14 +618,10 @@ def _direct_compress(screen: bool, buf: bytes, in_off, in_len, stride: int,
     d_out = torch.full((n_blocks * stride,), corpus.GUARD,
                        dtype=torch.uint8, device="cuda")
     d_lens = torch.full((n_blocks,), -1, dtype=torch.int32, device="cuda")
-    fn = lib.sy_lz4_compress_blocks_gpu2 if screen \
-        else lib.sy_lz4_compress_blocks_gpu
-    rc = fn(ctypes.c_void_p(d_data.data_ptr()),
-            ctypes.c_void_p(d_off.data_ptr()),
-            ctypes.c_void_p(d_len.data_ptr()),
-            ctypes.c_void_p(d_out.data_ptr()), ctypes.c_uint64(stride),
-            ctypes.c_void_p(d_lens.data_ptr()), ctypes.c_uint32(n_blocks),
-            ctypes.c_uint32(raw_cap), ops._stream())
+    rc = ops._call("sy_lz4_compress_blocks_gpu2" if screen
+                   else "sy_lz4_compress_blocks_gpu",
+                   d_data, d_off, d_len, d_out, stride, d_lens, n_blocks,
+                   raw_cap)
     assert rc == 0
     torch.cuda.synchronize()
     return d_out.cpu().numpy(), d_lens.cpu().numpy().view(np.uint32)
