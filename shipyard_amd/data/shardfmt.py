@@ -1380,6 +1380,210 @@ def decode_rows_device(d_comp, idx: ShardIndex, starts, counts, device,
                         row_elems, pad)
 
 
+# ------------------------------------------------------------- row writes
+def _narrow_types(dst_dtype):
+    """(element bytes, numpy dtype, smallest value, largest value) of a
+    row writer's destination type; ValueError for an unknown one."""
+    import numpy as np
+
+    from shipyard_amd import ops
+
+    size, signed = ops.narrow_sizes(dst_dtype)
+    bits = 8 * size
+    lo, hi = (-(1 << (bits - 1)), (1 << (bits - 1)) - 1) if signed else \
+        (0, (1 << bits) - 1)
+    return size, np.dtype(f"<{'i' if signed else 'u'}{size}"), lo, hi
+
+
+def _row_start(counts, n: int, row_elems: int):
+    """``counts`` (a host sequence, a numpy array or a tensor, which is
+    copied to the host) checked against the ``[n, row_elems]`` batch
+    they describe, as their exclusive prefix sum: a numpy int64 array of
+    ``n + 1`` entries.  ValueError names the first bad row."""
+    import numpy as np
+
+    if hasattr(counts, "detach"):  # a tensor: one D2H when on a device
+        counts = counts.detach().cpu().numpy()
+    counts = np.ascontiguousarray(counts, dtype=np.int64).reshape(-1)
+    if len(counts) != n:
+        raise ValueError(f"rows: {len(counts)} counts for {n} rows")
+    bad = (counts < 0) | (counts > row_elems)
+    if bad.any():
+        i = int(np.argmax(bad))
+        raise ValueError(
+            f"rows: row {i} has count {int(counts[i])}, must be 0.."
+            f"{row_elems} (row_elems)")
+    row_start = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(counts, out=row_start[1:])
+    return row_start
+
+
+def _stream_row(row_start, index: int) -> int:
+    """The row that holds stream element ``index``: the last one that
+    starts at or before it (rows in front of it that start there too
+    are empty)."""
+    import numpy as np
+
+    return int(np.searchsorted(row_start, index, side="right")) - 1
+
+
+def _misfit_error(row_start, index: int, value: int, dst_dtype, lo: int,
+                  hi: int) -> ValueError:
+    """The error of both row writers for the value at stream index
+    ``index``, the first one that ``dst_dtype`` cannot represent."""
+    row = _stream_row(row_start, index)
+    return ValueError(
+        f"rows: row {row}, column {index - int(row_start[row])} holds "
+        f"{value}, which {dst_dtype} ({lo}..{hi}) cannot represent")
+
+
+def narrow_rows_numpy(rows, counts, dst_dtype):
+    """CPU reference of the row writers: the live prefix of every row of
+    the ``[n, T]`` int32 or int64 array ``rows`` (``counts[i]`` elements
+    of row ``i``; what lies behind them is padding and is never looked
+    at) as one dense stream of little-endian ``dst_dtype`` elements
+    (``u1``, ``u2``, ``i2``, ``u4``, ``i4``).  Returns ``(bytes,
+    row_start)``: ``row_start`` is the exclusive prefix sum of the
+    counts, a numpy int64 array of ``n + 1`` entries in elements, so row
+    ``i`` is elements ``row_start[i]:row_start[i + 1]`` of the stream
+    and ``row_start[:-1]``, ``np.diff(row_start)`` are the ``starts``
+    and ``counts`` of the row readers.
+
+    ValueError for ``rows`` that is not a 2-D int32/int64 array, an
+    unknown ``dst_dtype``, counts of another length than ``n`` or
+    outside ``0..T`` (the first bad row is named), and for a live value
+    that ``dst_dtype`` cannot represent: the first one in stream order,
+    with its row, column and value."""
+    import numpy as np
+
+    rows = np.asarray(rows)
+    if rows.ndim != 2 or rows.dtype not in (np.dtype(np.int32),
+                                            np.dtype(np.int64)):
+        raise ValueError(
+            "rows: the batch must be a 2-D int32 or int64 array, not "
+            f"{rows.ndim}-D {rows.dtype}")
+    _, dst_np, lo, hi = _narrow_types(dst_dtype)
+    n, row_elems = rows.shape
+    row_start = _row_start(counts, n, row_elems)
+    live = np.arange(row_elems)[None, :] < np.diff(row_start)[:, None]
+    vals = rows[live]  # row-major: stream order
+    bad = (vals < lo) | (vals > hi)
+    if bad.any():
+        e = int(np.argmax(bad))
+        raise _misfit_error(row_start, e, int(vals[e]), dst_dtype, lo, hi)
+    return vals.astype(dst_np).tobytes(), row_start
+
+
+def narrow_rows_device(rows, counts, dst_dtype):
+    """``narrow_rows_numpy`` on the GPU: ``rows`` is an ``[n, T]`` int32
+    or int64 CUDA tensor, the stream comes back as a uint8 CUDA tensor
+    of ``row_start[n] * S`` bytes next to the numpy ``row_start``.
+    Streams of several batches can be concatenated (their ``row_start``
+    shifted) and handed to ``pack_gpu``.
+
+    ``counts`` may be a host sequence, a numpy array or a device tensor
+    (one D2H); they are checked on the host as in ``narrow_rows_numpy``
+    before anything is launched.  Then the prefix sum is uploaded,
+    ``ops.compact_narrow`` makes one launch, and its status word is read
+    back, the one synchronise of the call.  A live value that
+    ``dst_dtype`` cannot represent raises the ValueError of
+    ``narrow_rows_numpy``, same first offender and same text; padding
+    columns are never loaded.  A ``rows`` that is not contiguous is
+    copied first."""
+    import torch
+
+    from shipyard_amd import ops
+
+    if not isinstance(rows, torch.Tensor) or rows.dim() != 2 or \
+            rows.dtype not in (torch.int32, torch.int64):
+        raise ValueError(
+            "rows: the batch must be a 2-D int32 or int64 tensor")
+    if not rows.is_cuda:
+        raise ValueError(f"rows: the batch is on {rows.device}, not on a "
+                         "GPU (narrow_rows_numpy is the CPU path)")
+    size, _, lo, hi = _narrow_types(dst_dtype)
+    n, row_elems = rows.shape
+    row_start = _row_start(counts, n, row_elems)
+    total = int(row_start[n])
+    stream = torch.empty(total * size, dtype=torch.uint8, device=rows.device)
+    if total == 0:
+        return stream, row_start
+    clean = (1 << 63) - 1
+    status = torch.full((1,), clean, dtype=torch.int64, device=rows.device)
+    rows = rows.contiguous()
+    ops.compact_narrow(rows, _to_device(row_start, rows.device), stream,
+                       dst_dtype, status)
+    first = int(status.item())  # the synchronise
+    if first != clean:
+        row = _stream_row(row_start, first)
+        value = int(rows[row, first - int(row_start[row])].item())
+        raise _misfit_error(row_start, first, value, dst_dtype, lo, hi)
+    return stream, row_start
+
+
+def pack_rows(rows, counts, dst_dtype, block_raw: int = DEFAULT_BLOCK_RAW,
+              shuffle_elem: int = 0, delta_elem: int = 0,
+              bitshuffle_elem: int = 0, workers: Optional[int] = None):
+    """Author a typed shard from a padded batch on the CPU:
+    ``narrow_rows_numpy`` followed by ``pack``.  Returns ``(shard bytes,
+    row_start)``; the shard's raw data is the stream of ``dst_dtype``
+    elements, and ``read_rows_cpu`` / ``ShardStager.stage_rows`` with
+    ``starts = row_start[:-1]``, ``counts = np.diff(row_start)`` and the
+    batch's pad give the batch back.  The offsets travel as a shard of
+    their own: ``pack(row_start.tobytes(), delta_elem=8,
+    bitshuffle_elem=8)``.  The filter keywords and ``workers`` are
+    ``pack``'s (``shuffle_elem`` of the element size suits token
+    ids)."""
+    elems = _filter_elems("pack_rows", locals())
+    stream, row_start = narrow_rows_numpy(rows, counts, dst_dtype)
+    return pack(stream, block_raw=block_raw, workers=workers,
+                **elems), row_start
+
+
+def pack_rows_gpu(rows, counts, dst_dtype,
+                  block_raw: int = DEFAULT_BLOCK_RAW, shuffle_elem: int = 0,
+                  delta_elem: int = 0, bitshuffle_elem: int = 0):
+    """``pack_rows`` on the GPU for an ``[n, T]`` CUDA tensor:
+    ``narrow_rows_device`` followed by ``pack_gpu`` on the stream, which
+    never leaves HBM in between.  ``block_raw`` and the filter keywords
+    are ``pack_gpu``'s and are checked before anything touches the
+    device.  Output equals ``pack_gpu`` of ``narrow_rows_numpy``'s
+    stream byte for byte."""
+    if not gpu_block_raw_ok(block_raw):
+        raise ValueError(
+            f"pack_rows_gpu: block_raw={block_raw} must be a multiple of "
+            f"{GPU_BLOCK_ALIGN} and at most {GPU_LZ4_BLOCK_MAX}")
+    elems = _filter_elems("pack_rows_gpu", locals())
+    stream, row_start = narrow_rows_device(rows, counts, dst_dtype)
+    return pack_gpu(stream, block_raw=block_raw, **elems), row_start
+
+
+def pack_rows_auto(rows, counts, dst_dtype,
+                   block_raw: int = DEFAULT_BLOCK_RAW,
+                   workers: Optional[int] = None,
+                   gpu_threshold: int = 1 << 20, shuffle_elem: int = 0,
+                   delta_elem: int = 0, bitshuffle_elem: int = 0):
+    """``pack_rows`` wherever the batch is.  A CUDA tensor is narrowed
+    on its device and written by ``pack_rows_gpu`` (by the CPU writer
+    from the copied-back stream when ``block_raw`` is one that the GPU
+    writer does not take).  A host batch is narrowed by
+    ``narrow_rows_numpy`` and its stream goes to ``pack_auto``, whose
+    rules decide: the GPU writer when a GPU is present, the stream
+    reaches ``gpu_threshold`` bytes and ``block_raw`` suits it, the CPU
+    writer otherwise."""
+    elems = _filter_elems("pack_rows_auto", locals())
+    if getattr(rows, "is_cuda", False):
+        if gpu_block_raw_ok(block_raw):
+            return pack_rows_gpu(rows, counts, dst_dtype,
+                                 block_raw=block_raw, **elems)
+        stream, row_start = narrow_rows_device(rows, counts, dst_dtype)
+        return pack(stream.cpu().numpy().tobytes(), block_raw=block_raw,
+                    workers=workers, **elems), row_start
+    stream, row_start = narrow_rows_numpy(rows, counts, dst_dtype)
+    return pack_auto(stream, block_raw=block_raw, workers=workers,
+                     gpu_threshold=gpu_threshold, **elems), row_start
+
+
 def unpack_gpu(buf: bytes, device=None, verify: bool = True):
     """GPU reader: upload payload once, LZ4-decode all blocks on the
     MI355X, CRC32C-verify the decoded bytes, return a uint8 CUDA tensor.

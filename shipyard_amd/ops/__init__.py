@@ -91,6 +91,7 @@ SIGNATURES = {
     "sy_gather_ranges": (_P, _U64, _P, _P, _P, _P, _P, _U32, _P),
     "sy_gather_widen": (_P, _P, _P, _P, _U32, _U32, _U32, _INT, _U32, _I64,
                         _P),
+    "sy_compact_narrow": (_P, _P, _P, _P, _U32, _U32, _U32, _U32, _INT, _P),
     "sy_byte_shuffle": _BLOCK_FILTER,
     "sy_delta_filter": _BLOCK_FILTER,
     "sy_bit_shuffle": _BLOCK_FILTER,
@@ -557,6 +558,100 @@ def gather_widen(src, src_off, counts, dst, src_dtype: str, pad: int):
         return
     _call("sy_gather_widen", src, src_off, counts, dst, n, row_elems, size,
           int(signed), dst_size, pad)
+
+
+def narrow_sizes(dst_dtype) -> tuple:
+    """(destination element bytes, signed) of a ``compact_narrow``
+    destination type, one of ``WIDEN_SRC_DTYPES``; ValueError for
+    anything else."""
+    if dst_dtype not in WIDEN_SRC_DTYPES:
+        raise ValueError(
+            f"compact_narrow: dst_dtype={dst_dtype!r} is not one of "
+            f"{sorted(WIDEN_SRC_DTYPES)}")
+    return WIDEN_SRC_DTYPES[dst_dtype]
+
+
+def compact_narrow(src, row_start, dst, dst_dtype: str, status):
+    """Typed row compaction, the inverse of ``gather_widen``: the live
+    prefix of every row of the ``[n, T]`` tensor ``src`` as one dense
+    little-endian stream of ``dst_dtype`` elements.  Element
+    ``row_start[i] + c`` of the stream, for
+    ``c < row_start[i + 1] - row_start[i]``, is ``src[i, c]`` reduced to
+    its low S bytes (S the size of ``dst_dtype``).
+
+    ``src`` is a contiguous 2-D ``torch.int32`` or ``torch.int64`` CUDA
+    tensor, whose base may be any multiple of its element size;
+    ``row_start`` is the exclusive prefix sum of the rows' live counts,
+    a contiguous 1-D int64 tensor of ``n + 1`` entries on ``src``'s
+    device (``row_start[0] == 0``, ``row_start[n]`` the total);
+    ``dst`` is a contiguous uint8 tensor on that device whose base is
+    16-byte aligned; ``dst_dtype`` is one of ``WIDEN_SRC_DTYPES``
+    (``u1``, ``u2``, ``i2``, ``u4``, ``i4``; ``i4`` from int32 is a
+    plain compaction); ``status`` is an int64 tensor of one element on
+    the device that the caller has set to ``INT64_MAX``
+    (``2**63 - 1``).
+
+    One launch (compact_narrow.hip) with no host sync, the total is read
+    on the device: every byte of ``dst[:total * S]`` is written exactly
+    once, no byte behind it is written, only live elements are loaded
+    (what the padding columns hold does not matter), and ``status``
+    receives the smallest stream index whose value ``dst_dtype`` cannot
+    represent (it keeps ``INT64_MAX`` when all fit).  A value that does
+    not fit is still stored, truncated; the caller is expected to read
+    ``status`` and discard the stream.
+
+    A ``src`` that is not a contiguous 2-D int32/int64 CUDA tensor, an
+    unknown ``dst_dtype``, a ``row_start`` of another dtype, shape,
+    length or device, a ``dst`` that is not contiguous uint8, is on
+    another device or is not 16-byte aligned, a ``status`` that is not
+    int64[1] on the device, ``n >= 2**32`` and
+    ``T > WIDEN_MAX_ROW_ELEMS`` are each a ValueError raised before any
+    launch; ``n == 0`` or ``T == 0`` is a no-op without a launch.
+
+    The caller guarantees, and nothing checks, that ``row_start``
+    ascends from 0 in steps of at most T, that ``dst`` holds
+    ``row_start[n] * S`` bytes and that it does not overlap ``src``:
+    the numbers are on the device, and looking at them here would cost
+    a synchronise (``shardfmt.narrow_rows_device`` builds ``row_start``
+    from counts it has checked on the host)."""
+    import torch
+
+    if src.dtype not in (torch.int32, torch.int64):
+        raise ValueError(
+            f"compact_narrow: src must be int32 or int64, not {src.dtype}")
+    if src.dim() != 2 or not src.is_contiguous():
+        raise ValueError("compact_narrow: src must be a contiguous [n, T] "
+                         "tensor")
+    if not src.is_cuda:
+        raise ValueError(
+            f"compact_narrow: src is on {src.device}, not on a GPU")
+    size, signed = narrow_sizes(dst_dtype)
+    _check_index_tensors("compact_narrow", src, ((row_start, "row_start"),))
+    n, row_elems = src.shape
+    if row_start.numel() != n + 1:
+        raise ValueError(
+            f"compact_narrow: {row_start.numel()} entries of row_start "
+            f"for {n} rows of src, must be {n + 1}")
+    if dst.dtype != torch.uint8 or not dst.is_contiguous():
+        raise ValueError(
+            "compact_narrow: dst must be a contiguous uint8 tensor")
+    if dst.device != src.device:
+        raise ValueError(
+            f"compact_narrow: dst is on {dst.device}, src on {src.device}")
+    _check_aligned16(dst, "compact_narrow: dst", advice=_CLONE_IT)
+    if status.dtype != torch.int64 or status.numel() != 1 or \
+            status.device != src.device:
+        raise ValueError(
+            "compact_narrow: status must be one int64 on src's device, not "
+            f"{status.numel()} of {status.dtype} on {status.device}")
+    if n >= 1 << 32 or row_elems > WIDEN_MAX_ROW_ELEMS:
+        raise ValueError(
+            "compact_narrow: at most 2**32 - 1 rows of at most "
+            f"{WIDEN_MAX_ROW_ELEMS} elements")
+    if n == 0 or row_elems == 0:
+        return
+    _call("sy_compact_narrow", src, row_start, dst, status, n, row_elems,
+          src.element_size(), size, int(signed))
 
 
 FILTER_ELEM_SIZES = (2, 4, 8)
