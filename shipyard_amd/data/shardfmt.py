@@ -1380,6 +1380,245 @@ def decode_rows_device(d_comp, idx: ShardIndex, starts, counts, device,
                         row_elems, pad)
 
 
+# ----------------------------------------------------------- packed reads
+def plan_packed_rows(counts, row_elems: int):
+    """Where every sample of a packed read goes: ``(row, col, n_rows)``,
+    two numpy int64 arrays as long as ``counts`` and the number of rows
+    used.  Next-fit in the caller's order: sample ``i`` goes directly
+    behind sample ``i - 1`` in the same row if it still fits
+    (``col + counts[i] <= row_elems``) and opens the next row at column
+    0 otherwise.  An empty sample takes the cursor's place and no
+    space; no samples at all give ``n_rows == 0``.  ValueError, naming
+    the first bad sample, for ``row_elems < 0``, a negative count and a
+    sample longer than a row.  The readers take ``row``/``col`` as
+    plain arguments: a caller with a better bin-packer brings its own
+    plan."""
+    import numpy as np
+
+    row_elems = int(row_elems)
+    if row_elems < 0:
+        raise ValueError(f"row_elems={row_elems} must not be negative")
+    counts = np.ascontiguousarray(counts, dtype=np.int64).reshape(-1)
+    bad = (counts < 0) | (counts > row_elems)
+    if bad.any():
+        i = int(np.argmax(bad))
+        raise ValueError(
+            f"packed: sample {i} has {int(counts[i])} elements, which is "
+            f"negative or more than row_elems={row_elems}")
+    row = np.empty(len(counts), dtype=np.int64)
+    col = np.empty(len(counts), dtype=np.int64)
+    r = c = 0
+    for i, n in enumerate(counts.tolist()):
+        if c + n > row_elems:
+            r, c = r + 1, 0
+        row[i], col[i] = r, c
+        c += n
+    return row, col, (r + 1 if len(counts) else 0)
+
+
+def _as_packed(starts, counts, row, col, n_rows: int, size: int,
+               raw_size: int, row_elems: int):
+    """The plan of a packed read, checked: ``starts``/``counts`` as
+    ``_as_rows`` gives them, ``row``/``col`` as numpy int64 arrays of
+    their length.  ValueError names the first bad sample in the
+    caller's order (of two samples that overlap, the later one)."""
+    import numpy as np
+
+    starts, counts = _as_rows(starts, counts, size, raw_size, row_elems)
+    row = np.ascontiguousarray(row, dtype=np.int64).reshape(-1)
+    col = np.ascontiguousarray(col, dtype=np.int64).reshape(-1)
+    if len(row) != len(starts) or len(col) != len(starts):
+        raise ValueError(
+            f"packed: {len(starts)} starts and counts but {len(row)} rows "
+            f"and {len(col)} columns")
+    n_rows, row_elems = int(n_rows), int(row_elems)
+    if n_rows < 0:
+        raise ValueError(f"n_rows={n_rows} must not be negative")
+    for bad, what in (
+            ((row < 0) | (row >= n_rows),
+             f"a row outside the {n_rows} rows"),
+            (col < 0, "a negative column"),
+            (col > row_elems - counts,
+             f"a last column behind row_elems={row_elems}")):
+        if bad.any():
+            i = int(np.argmax(bad))
+            raise ValueError(
+                f"packed: sample {i} (row {int(row[i])}, column "
+                f"{int(col[i])}, count {int(counts[i])}) has {what}")
+    order, dst_start, _ = _packed_lists(counts, row, col, row_elems)
+    if len(order) > 1:
+        ends = dst_start + counts[order]
+        # the sample that reaches furthest among those sorted before k
+        reach = np.maximum.accumulate(ends)[:-1]
+        hit = np.flatnonzero(dst_start[1:] < reach)
+        if len(hit):
+            holder = np.flatnonzero(np.concatenate(([True], ends[1:] >
+                                                    reach)))
+            # of every overlapping pair the later sample in caller order
+            other = order[holder[np.searchsorted(holder, hit, "right") - 1]]
+            later = np.maximum(order[hit + 1], other)
+            k = int(np.argmin(later))
+            i = int(later[k])
+            j = int(min(order[hit[k] + 1], other[k]))
+            raise ValueError(
+                f"packed: sample {i} (row {int(row[i])}, columns "
+                f"{int(col[i])}..{int(col[i] + counts[i]) - 1}) overlaps "
+                f"sample {j} (columns {int(col[j])}.."
+                f"{int(col[j] + counts[j]) - 1})")
+    return starts, counts, row, col
+
+
+def _packed_lists(counts, row, col, row_elems: int):
+    """The non-empty samples of a packed plan in destination order
+    (stable, by ``row * row_elems + col``): their indices in the
+    caller's order, their flat destination starts and their labels
+    (1 + the number of non-empty samples of the same row at a smaller
+    column), as numpy int64, int64 and int32 arrays."""
+    import numpy as np
+
+    live = np.flatnonzero(counts > 0)
+    key = row[live] * int(row_elems) + col[live]
+    by_dst = np.argsort(key, kind="stable")
+    order, dst_start = live[by_dst], key[by_dst]
+    rows = row[order]
+    labels = np.arange(len(order)) - np.searchsorted(rows, rows, "left") + 1
+    return order, dst_start, labels.astype(np.int32)
+
+
+def read_packed_cpu(buf: bytes, starts, counts, row, col, n_rows: int,
+                    src_dtype, out_dtype, row_elems: int, pad: int,
+                    verify: bool = True):
+    """CPU reference of the packed readers: numpy arrays
+    ``(tokens, segment_ids, positions)`` of shape ``[n_rows, row_elems]``,
+    ``tokens`` of ``out_dtype`` (int32 or int64) and the other two
+    int32.  Sample ``i``, the ``counts[i]`` elements of type
+    ``src_dtype`` from element ``starts[i]`` of the shard in ``buf``,
+    lands widened at ``tokens[row[i], col[i]:col[i] + counts[i]]``;
+    there ``positions`` counts from 0 and ``segment_ids`` holds the
+    sample's label, 1 + the number of non-empty samples of the same row
+    at a smaller column.  Every other element holds ``pad`` in
+    ``tokens`` and 0 in the other two.  Built on ``read_ranges_cpu``
+    (only touched blocks are decoded and verified).  Each bad argument
+    is a ValueError, see ``decode_packed_device``."""
+    import numpy as np
+
+    idx = read_index(buf)
+    size, src_np, out_np, pad = _row_types(src_dtype, out_dtype, pad)
+    starts, counts, row, col = _as_packed(
+        starts, counts, row, col, n_rows, size, idx.raw_size, row_elems)
+    shape = (int(n_rows), int(row_elems))
+    tokens = np.full(shape, pad, dtype=out_np)
+    segment_ids = np.zeros(shape, dtype=np.int32)
+    positions = np.zeros(shape, dtype=np.int32)
+    order, dst_start, labels = _packed_lists(counts, row, col, row_elems)
+    if len(order):
+        n = counts[order]
+        data = read_ranges_cpu(buf, starts[order] * size, n * size,
+                               verify=verify)
+        # the ranges come back concatenated in destination order
+        first = np.cumsum(n) - n
+        within = np.arange(int(n.sum())) - np.repeat(first, n)
+        at = np.repeat(dst_start, n) + within
+        tokens.reshape(-1)[at] = np.frombuffer(data, dtype=src_np)
+        segment_ids.reshape(-1)[at] = np.repeat(labels, n)
+        positions.reshape(-1)[at] = within
+    return tokens, segment_ids, positions
+
+
+def _decode_packed(d_comp, idx: ShardIndex, sel, comp_off, starts, counts,
+                   row, col, n_rows: int, device, verify: bool, src_dtype,
+                   out_np, row_elems: int, pad: int):
+    """The device side of a packed read, shared by
+    ``decode_packed_device`` and ``ShardStager.stage_packed``: the
+    non-empty samples in destination order (``_packed_lists``),
+    ``_decode_selected`` for their byte ranges, then one
+    ``ops.gather_pack`` launch.  The plan is checked (``_as_packed``),
+    the index is validated and ``_row_types`` has passed."""
+    import numpy as np
+    import torch
+
+    from shipyard_amd import ops
+
+    shape = (int(n_rows), int(row_elems))
+    tokens = torch.empty(shape, dtype=getattr(torch, out_np.name),
+                         device=device)
+    segment_ids = torch.empty(shape, dtype=torch.int32, device=device)
+    positions = torch.empty(shape, dtype=torch.int32, device=device)
+    if shape[0] == 0 or shape[1] == 0:
+        return tokens, segment_ids, positions
+    size = ops.widen_sizes(src_dtype, 8 * out_np.itemsize)[0]
+    order, dst_start, labels = _packed_lists(counts, row, col, row_elems)
+    n = counts[order]
+    if len(sel):
+        scratch, src_off = _decode_selected(
+            d_comp, idx, sel, comp_off, starts[order] * size, n * size,
+            device, verify)
+    else:  # nothing but empty samples: nothing to decode, all of it pad
+        scratch = torch.empty(0, dtype=torch.uint8, device=device)
+        src_off = _to_device(np.zeros(0, dtype=np.int64), device)
+    ops.gather_pack(scratch, src_off, _to_device(n, device),
+                    _to_device(dst_start, device),
+                    _to_device(labels, device), tokens, segment_ids,
+                    positions, src_dtype, pad)
+    return tokens, segment_ids, positions
+
+
+def decode_packed_device(d_comp, idx: ShardIndex, starts, counts, row, col,
+                         n_rows: int, device, src_dtype, out_dtype,
+                         row_elems: int, pad: int, verify: bool = True):
+    """Packed typed read of an uploaded shard payload in HBM: several
+    samples per row instead of one sample and its padding.  Returns
+    device tensors ``(tokens, segment_ids, positions)`` of shape
+    ``[n_rows, row_elems]``, ``tokens`` of ``out_dtype`` (int32 or
+    int64), the other two int32.
+
+    Sample ``i`` is the ``counts[i]`` elements of type ``src_dtype``
+    from element ``starts[i]`` of the raw data (units and types as for
+    ``decode_rows_device``).  It lands, widened, at
+    ``tokens[row[i], col[i]:col[i] + counts[i]]``.  There ``positions``
+    is ``0 .. counts[i] - 1``, position ids that restart at every
+    sample, and ``segment_ids`` is the sample's label: 1 + the number
+    of non-empty samples of the same row at a smaller column, so
+    ``segment_ids[r, a] == segment_ids[r, b] != 0`` is the
+    block-diagonal attention mask.  An empty sample appears nowhere and
+    takes no label.  Every element that no sample covers, a gap inside
+    a row as well as its tail, holds ``pad`` in ``tokens`` and 0 in the
+    other two.  Samples come in any order and may repeat or overlap in
+    the source, not in the destination.  ``plan_packed_rows`` makes a
+    next-fit ``row``/``col``/``n_rows``; any other plan that passes the
+    checks will do.
+
+    Everything up to the last step is ``decode_rows_device``'s: the
+    table is validated, the blocks that hold an element of a sample are
+    selected, decoded into the compact scratch, unfiltered and, with
+    ``verify``, CRC-checked (only those blocks).  The non-empty samples
+    are stable-sorted by destination on the host and ``ops.gather_pack``
+    writes all three outputs in one launch, nothing pre-filled.
+
+    Each of these is a ValueError raised before a tensor is made or a
+    kernel launched, naming the first bad sample in the caller's order:
+    everything ``decode_rows_device`` checks for ``starts``/``counts``,
+    the types and ``pad``; unequal lengths of the four sequences;
+    ``n_rows < 0``; a ``row[i]`` outside ``0 .. n_rows - 1``;
+    ``col[i] < 0``; ``col[i] + counts[i] > row_elems``; two non-empty
+    samples of one row that overlap (named: the later one in the
+    caller's order).  ``n_rows == 0`` or ``row_elems == 0``: empty
+    tensors and no launch.  Samples that are all empty: ``pad`` and
+    zeros, written by the kernel, and nothing is decoded.
+
+    Peak HBM on top of the payload is that of ``decode_rows_device``
+    with R = ``n_rows * row_elems * (out_dtype.itemsize + 8)``."""
+    validate_index(idx, d_comp.numel(), for_gpu=True)
+    size, _, out_np, pad = _row_types(src_dtype, out_dtype, pad)
+    starts, counts, row, col = _as_packed(
+        starts, counts, row, col, n_rows, size, idx.raw_size, row_elems)
+    sel = _select_blocks(starts * size, counts * size, int(idx.block_raw),
+                         idx.n_blocks)
+    return _decode_packed(d_comp, idx, sel, idx.table["comp_off"][sel],
+                          starts, counts, row, col, n_rows, device, verify,
+                          src_dtype, out_np, row_elems, pad)
+
+
 # ------------------------------------------------------------- row writes
 def _narrow_types(dst_dtype):
     """(element bytes, numpy dtype, smallest value, largest value) of a

@@ -232,8 +232,43 @@ class ShardStager:
 
         return self._stage_selected(path, plan, "rows")
 
+    def stage_packed(self, path, starts, counts, row, col, n_rows: int,
+                     src_dtype, out_dtype, row_elems: int,
+                     pad: int) -> "tuple":
+        """Stage typed samples of one SYSHARD file into HBM packed,
+        several per row: ``[n_rows, row_elems]`` tensors
+        ``(tokens, segment_ids, positions)`` in which sample ``i``, the
+        ``counts[i]`` elements of type ``src_dtype`` from element
+        ``starts[i]`` of the raw data, lies widened at
+        ``tokens[row[i], col[i]:col[i] + counts[i]]``, labelled in
+        ``segment_ids`` and counted from 0 in ``positions``; every other
+        element is ``pad``, 0 and 0.  Returns
+        ((tokens, segment_ids, positions), StageResult); the three
+        tensors are what ``shardfmt.decode_packed_device`` returns for
+        the same arguments, and the two share their code.
+        ``shardfmt.plan_packed_rows`` makes a next-fit plan.
+
+        The file is read exactly as ``stage_rows`` reads it.
+        ``StageResult.file_bytes`` counts the bytes read and
+        ``raw_bytes`` the source bytes of the samples."""
+
+        def plan(idx):
+            size, _, out_np, p = shardfmt._row_types(src_dtype, out_dtype,
+                                                     pad)
+            s, c, r, k = shardfmt._as_packed(
+                starts, counts, row, col, n_rows, size, idx.raw_size,
+                row_elems)
+            return s * size, c * size, lambda d_payload, sel, comp_off: \
+                shardfmt._decode_packed(
+                    d_payload, idx, sel, comp_off, s, c, r, k, n_rows,
+                    self.device, self.verify, src_dtype, out_np, row_elems,
+                    p)
+
+        return self._stage_selected(path, plan, "packed samples")
+
     def _stage_selected(self, path, plan, what: str) -> "tuple":
-        """The file side of ``stage_ranges`` and ``stage_rows``.
+        """The file side of ``stage_ranges``, ``stage_rows`` and
+        ``stage_packed``.
         ``plan(idx)`` looks at the request once the table is validated:
         it raises ValueError or returns the byte ranges the request
         needs (offs, lens) and ``decode(d_payload, sel, comp_off)``,

@@ -92,6 +92,8 @@ SIGNATURES = {
     "sy_gather_widen": (_P, _P, _P, _P, _U32, _U32, _U32, _INT, _U32, _I64,
                         _P),
     "sy_compact_narrow": (_P, _P, _P, _P, _U32, _U32, _U32, _U32, _INT, _P),
+    "sy_gather_pack": (_P, _P, _P, _P, _P, _P, _P, _P, _U32, _U64, _U32, _INT,
+                       _U32, _I64, _P),
     "sy_byte_shuffle": _BLOCK_FILTER,
     "sy_delta_filter": _BLOCK_FILTER,
     "sy_bit_shuffle": _BLOCK_FILTER,
@@ -558,6 +560,122 @@ def gather_widen(src, src_off, counts, dst, src_dtype: str, pad: int):
         return
     _call("sy_gather_widen", src, src_off, counts, dst, n, row_elems, size,
           int(signed), dst_size, pad)
+
+
+GATHER_PACK_MAX_SEGMENTS = (1 << 31) - 1
+
+
+def gather_pack(src, src_off, counts, dst_start, labels, tokens,
+                segment_ids, positions, src_dtype: str, pad: int):
+    """Packed typed gather: several source runs per row of a batch, with
+    the two tensors that say which run an element belongs to.  For every
+    segment ``i`` of the m given, with ``e = dst_start[i]`` an index into
+    the flattened ``[n, T]`` outputs and ``c = counts[i]``:
+    ``tokens.view(-1)[e:e + c]`` receives the ``c`` elements of type
+    ``src_dtype`` that start at byte ``src_off[i]`` of ``src``,
+    zero-extended (``u1``, ``u2``, ``u4``) or sign-extended (``i2``,
+    ``i4``); ``segment_ids.view(-1)[e:e + c]`` receives ``labels[i]``
+    and ``positions.view(-1)[e:e + c]`` receives ``0, 1, ..., c - 1``.
+    Every element that no segment covers, in front of the first one, in
+    a gap or behind the last one, receives ``pad`` in ``tokens`` and 0
+    in the other two.  A segment may run across a row end.
+
+    ``src`` is a contiguous uint8 CUDA tensor whose base pointer is a
+    multiple of the source element size S; ``src_off`` (int64, bytes,
+    multiples of S), ``counts`` (int64, elements, all > 0) and
+    ``dst_start`` (int64, flat elements) are 1-D tensors of length m on
+    its device and ``labels`` is an int32 one; ``tokens`` is a
+    contiguous 2-D ``torch.int32`` or ``torch.int64`` tensor and
+    ``segment_ids`` and ``positions`` are contiguous ``torch.int32``
+    tensors of its shape, all three with a 16-byte-aligned base (fresh
+    tensors are; the kernel stores whole uint4s from the base and has no
+    path for an unaligned head).  Only value-preserving conversions, as
+    for ``gather_widen``.  Source runs may overlap or repeat.
+
+    One launch (gather_pack.hip) and no host sync: every element of the
+    three outputs is written exactly once, so the caller does not
+    pre-fill them, nothing outside them is written, and of ``src`` only
+    the bytes of the segments are loaded.
+
+    A ``src`` that is not contiguous uint8, a wrong dtype, shape or
+    device of a list or of an output, a non-contiguous tensor, tensors
+    that are not on a GPU, lists of unequal lengths, an unknown or
+    forbidden conversion, a ``pad`` that ``tokens.dtype`` cannot hold, a
+    ``src`` base that is no multiple of S, an output base that is no
+    multiple of 16 and more than ``GATHER_PACK_MAX_SEGMENTS``
+    (2**31 - 1) segments are each a ValueError raised before any
+    launch.  ``n * T == 0`` is a no-op without a launch; ``m == 0`` is
+    legal and writes an all-pad output.
+
+    The caller guarantees, and nothing checks, that ``dst_start``
+    ascends with ``dst_start[i] + counts[i] <= dst_start[i + 1]``, that
+    ``0 < counts[i] < 2**31`` and the last segment ends inside ``n * T``,
+    that every segment lies inside ``src``, and that no output overlaps
+    ``src`` or another output: the numbers are on the device, and
+    looking at them here would cost a synchronise
+    (``shardfmt.decode_packed_device`` checks its plan on the host,
+    where it comes from)."""
+    import torch
+
+    if src.dtype != torch.uint8 or not src.is_contiguous():
+        raise ValueError(
+            "gather_pack: src must be a contiguous uint8 tensor")
+    if tokens.dtype not in (torch.int32, torch.int64):
+        raise ValueError(
+            f"gather_pack: tokens must be int32 or int64, not {tokens.dtype}")
+    if tokens.dim() != 2 or not tokens.is_contiguous():
+        raise ValueError("gather_pack: tokens must be a contiguous [n, T] "
+                         "tensor")
+    for t, which in ((segment_ids, "segment_ids"), (positions, "positions")):
+        if t.dtype != torch.int32:
+            raise ValueError(
+                f"gather_pack: {which} must be int32, not {t.dtype}")
+        if t.shape != tokens.shape or not t.is_contiguous():
+            raise ValueError(
+                f"gather_pack: {which} must be a contiguous tensor of "
+                f"tokens' shape {tuple(tokens.shape)}, not {tuple(t.shape)}")
+    dst_size = tokens.element_size()
+    size, signed = widen_sizes(src_dtype, 8 * dst_size)
+    pad = check_widen_pad(pad, 8 * dst_size)
+    if src.data_ptr() % size:
+        raise ValueError(
+            f"gather_pack: src base pointer must be a multiple of the "
+            f"{size}-byte element (tensor storage offset "
+            f"{src.storage_offset()})")
+    _check_index_tensors("gather_pack", src, (
+        (src_off, "src_off"), (counts, "counts"), (dst_start, "dst_start")))
+    if labels.dtype != torch.int32:
+        raise ValueError(
+            f"gather_pack: labels must be int32, not {labels.dtype}")
+    if labels.dim() != 1 or not labels.is_contiguous():
+        raise ValueError("gather_pack: labels must be a contiguous 1-D tensor")
+    if labels.device != src.device:
+        raise ValueError(
+            f"gather_pack: labels is on {labels.device}, src on {src.device}")
+    m = counts.numel()
+    if src_off.numel() != m or dst_start.numel() != m or labels.numel() != m:
+        raise ValueError(
+            f"gather_pack: {src_off.numel()} source offsets, {m} counts, "
+            f"{dst_start.numel()} destination starts and {labels.numel()} "
+            "labels")
+    if m > GATHER_PACK_MAX_SEGMENTS:
+        raise ValueError(
+            f"gather_pack: at most {GATHER_PACK_MAX_SEGMENTS} segments")
+    for t, which in ((tokens, "tokens"), (segment_ids, "segment_ids"),
+                     (positions, "positions")):
+        if t.device != src.device:
+            raise ValueError(
+                f"gather_pack: {which} is on {t.device}, src on {src.device}")
+        _check_aligned16(t, f"gather_pack: {which}", advice=_CLONE_IT)
+    if not src.is_cuda:
+        raise ValueError(
+            f"gather_pack: src and the outputs are on {src.device}, not on "
+            "a GPU")
+    if tokens.numel() == 0:
+        return
+    _call("sy_gather_pack", src, src_off, counts, dst_start, labels, tokens,
+          segment_ids, positions, m, tokens.numel(), size, int(signed),
+          dst_size, pad)
 
 
 def narrow_sizes(dst_dtype) -> tuple:

@@ -21,7 +21,7 @@ SOURCES = ["crc32c.hip", "lz4_decode.hip", "sha256.hip",
            "gather_copy.hip", "stager.cpp", "lz4_compress.cpp",
            "lz4_compress_gpu.hip", "byte_shuffle.hip",
            "delta_filter.hip", "bit_shuffle.hip", "gather_ranges.hip",
-           "gather_widen.hip", "compact_narrow.hip"]
+           "gather_widen.hip", "compact_narrow.hip", "gather_pack.hip"]
 HEADERS = ["common.h", "shuffle_tile.h"]
 
 
